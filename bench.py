@@ -12,7 +12,11 @@ A step = one batch of the chunk: batch gather, forward, fused LogSoftmax/NLL hea
 Multi-GPU: one process per GPU (torch.distributed.run), chunk-level data parallelism: every rank
 trains its own chunk slice at the cfg batch size (weak scaling), gradients averaged every step.
 
-Prints ONE JSON line (rank 0).
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints
+ONE JSON line (rank 0).  `--dump-outputs DIR` also writes what the last timed step left behind as
+DIR/<name>.npy; `--full` adds every other leg to the line: the per-launch profile and roofline,
+the fp32 / bf16x3 entries, the batch sweep, the sequence configurations, the posterior checks
+against the oracle and the CPU baselines.
 """
 import argparse
 import json
@@ -361,30 +365,20 @@ def seq_entry(name, steps, warmup, with_cpu, cpu_seconds, prec="fp32"):
     return out
 
 
-def measure_mlp(prec, args, rank, world, allreduce):
-    """The C2 step at `prec`: live per-launch profile -> dominant entry point, the captured
-    step's timed region (exactly args.steps batches), the dominant launch's roofline."""
-    from pkc import _lib
-    eng, chunk, prep_s, nets = build(prec, args.batch, rank, world)
-    # per-launch device times of warm eager steps -> dominant kernel + its roofline inputs
-    for _ in range(3):
-        eng.train_step(allreduce)
+def launch_profile(eng, nprof=5):
+    """Per-launch device times of `nprof` warm eager steps: (per-label [launches, ms, flops,
+    bytes] averages, per-entry-point totals of one step, the last step's launch list)."""
     agg = {}
-    NPROF = 5
-    for _ in range(NPROF):
+    for _ in range(nprof):
         prof = eng.profile_step()
         for label, fn, fl, nb, ms in prof:
             a = agg.setdefault(label, [0, 0.0, 0.0, 0.0])
             a[0] += 1
-            a[1] += ms / NPROF
+            a[1] += ms / nprof
             a[2] += fl
             a[3] += nb
     for v in agg.values():
-        v[0] //= NPROF
-    # dominant kernel = the libpkc entry point with the largest in-step device time, measured
-    # live with HIP events as (step graph) - (step graph without its launches) for the three
-    # largest candidates by eager time (after this the weights are stale: it runs after the
-    # timed region, or alone in a counter run)
+        v[0] //= nprof
     by_fn = {}
     for label, fn, fl, nb, ms in prof:
         f = by_fn.setdefault(fn, {"labels": set(), "launches": 0, "flops": 0.0, "bytes": 0.0,
@@ -394,9 +388,72 @@ def measure_mlp(prec, args, rank, world, allreduce):
         f["flops"] += fl
         f["bytes"] += nb
         f["eager_ms"] += ms
-    cands = sorted(by_fn, key=lambda k: -by_fn[k]["eager_ms"])[:3]
+    return agg, by_fn, prof
+
+
+DUMP_MAX_BYTES = 60 * 1000 * 1000      # --dump-outputs: all arrays together stay below 64 MB
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: tensor / ndarray} as dirname/<name>.npy (float32; other dtypes as float64).
+    When the arrays together exceed DUMP_MAX_BYTES, every array above the equal share is cut to a
+    sample of its flattened elements at fixed positions (drawn once from RandomState(0) per array
+    size and sorted), so two runs or two builds dump the same elements."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    share = None
+    if sum(a.nbytes for a in host.values()) > DUMP_MAX_BYTES:
+        # the share that fills the budget: small arrays whole, the rest cut to `share` bytes each
+        left, todo = DUMP_MAX_BYTES, sorted(host.values(), key=lambda a: a.nbytes)
+        while todo and todo[0].nbytes * len(todo) <= left:
+            left -= todo.pop(0).nbytes
+        share = left // len(todo)
+    picks = {}
+    for name, a in host.items():
+        if share is not None and a.nbytes > share:
+            n = share // a.itemsize
+            if (a.size, n) not in picks:
+                picks[a.size, n] = np.sort(np.random.RandomState(0).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[picks[a.size, n]]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def engine_outputs(eng, nets, heads):
+    """What a caller of the training path holds after its last step: the step's loss / error, the
+    chunk's running totals, the posteriors of the last batch (`heads`: [model] output names) and
+    every parameter and buffer of the trained nets."""
+    loss, err = eng.loss_values()
+    out = {"loss_err": np.array([loss, err]), "chunk_totals": np.array(eng.chunk_totals())}
+    for h in heads:
+        out[h] = eng.head_output(h).float()
+    eng.sync_state()
+    for arch, net in nets.items():
+        for k, v in net.state_dict().items():
+            out["%s.%s" % (arch, k)] = v
+    return out
+
+
+def measure_mlp(prec, args, rank, world, allreduce, full=True, dump=None):
+    """The C2 step at `prec`: the captured step's timed region (exactly args.steps batches);
+    full: a live per-launch profile before it -> dominant entry point, and the dominant launch's
+    roofline after it.  dump: directory for the arrays of the last timed step (dump_outputs)."""
+    from pkc import _lib
+    eng, chunk, prep_s, nets = build(prec, args.batch, rank, world)
+    for _ in range(3):
+        eng.train_step(allreduce)
+    if full or args.pmc_replay:
+        # per-launch device times of warm eager steps -> dominant kernel + its roofline inputs
+        agg, by_fn, prof = launch_profile(eng)
+        cands = sorted(by_fn, key=lambda k: -by_fn[k]["eager_ms"])[:3]
 
     def pick_dominant():
+        # dominant kernel = the libpkc entry point with the largest in-step device time, measured
+        # live with HIP events as (step graph) - (step graph without its launches) for the three
+        # largest candidates by eager time (after this the weights are stale: it runs after the
+        # timed region, or alone in a counter run)
         costs = {fn: eng.step_cost_of(by_fn[fn]["labels"])[0] for fn in cands}
         fn = max(costs, key=costs.get)
         return fn, costs[fn]
@@ -414,13 +471,22 @@ def measure_mlp(prec, args, rank, world, allreduce):
     dt = time_steps(eng, args.steps, args.warmup, allreduce, world)
     loss_sum, err_sum = eng.chunk_totals()
     n_done = args.warmup + args.steps
+    pname = {v: k for k, v in PREC_NAMES.items()}[prec]
+    if dump:
+        dump_outputs(dump, engine_outputs(eng, nets, ("out_dnn2", "out_dnn3")))
+    frames = args.steps * args.batch * world
+    res = {"value": round(frames / dt, 1), "ms_per_step": round(dt / args.steps * 1e3, 4),
+           "dtype": pname, "graph_launches_per_step": graph_lps,
+           "chunk_frames_per_rank": chunk.n_rows, "chunk_prep_s": round(prep_s, 3),
+           "mean_loss": round(loss_sum / max(1, n_done), 4)}
+    if not full:
+        return res
     dom_fn, dom_us = pick_dominant()
     d = by_fn[dom_fn]
     cnt = d["launches"]
     per_launch_fl = d["flops"] / cnt
     per_launch_nb = d["bytes"] / cnt
     avg_ms = dom_us / cnt * 1e-3
-    pname = {v: k for k, v in PREC_NAMES.items()}[prec]
     traffic = pmc_traffic(dom_fn if pname == "bf16" else dom_fn + "@" + pname)
     del eng
     torch.cuda.empty_cache()
@@ -432,22 +498,18 @@ def measure_mlp(prec, args, rank, world, allreduce):
     else:
         bound, peak, unit = "hbm", HBM_PEAK_GBS, "GB/s"
         achieved = per_launch_nb / (avg_ms * 1e-3) / 1e9
-    frames = args.steps * args.batch * world
-    return {"value": round(frames / dt, 1), "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "dtype": pname,
-            "roofline": {"kernel": dom_fn, "labels": sorted(d["labels"]), "bound": bound,
-                         "achieved": round(achieved, 2), "peak": peak, "unit": unit,
-                         "frac": round(achieved / peak, 4), "traffic": traffic,
-                         "avg_launch_us": round(avg_ms * 1e3, 3), "launches_per_step": cnt,
-                         "algorithmic_bytes_per_launch": per_launch_nb,
-                         "algorithmic_flops_per_launch": per_launch_fl,
-                         "mfma_tflops_per_launch": round(per_launch_fl / (avg_ms * 1e-3) / 1e12, 2)},
-            "launches_per_step": len(prof),
-            "graph_launches_per_step": graph_lps,
-            "step_breakdown_us": {k: round(v[1] * 1e3, 2) for k, v in
-                                  sorted(agg.items(), key=lambda kv: -kv[1][1])},
-            "chunk_frames_per_rank": chunk.n_rows, "chunk_prep_s": round(prep_s, 3),
-            "mean_loss": round(loss_sum / max(1, n_done), 4)}
+    res.update({
+        "roofline": {"kernel": dom_fn, "labels": sorted(d["labels"]), "bound": bound,
+                     "achieved": round(achieved, 2), "peak": peak, "unit": unit,
+                     "frac": round(achieved / peak, 4), "traffic": traffic,
+                     "avg_launch_us": round(avg_ms * 1e3, 3), "launches_per_step": cnt,
+                     "algorithmic_bytes_per_launch": per_launch_nb,
+                     "algorithmic_flops_per_launch": per_launch_fl,
+                     "mfma_tflops_per_launch": round(per_launch_fl / (avg_ms * 1e-3) / 1e12, 2)},
+        "launches_per_step": len(prof),
+        "step_breakdown_us": {k: round(v[1] * 1e3, 2) for k, v in
+                              sorted(agg.items(), key=lambda kv: -kv[1][1])}})
+    return res
 
 
 WORKLOADS = {
@@ -467,10 +529,14 @@ def seq_main(args, rank, world, allreduce):
     every rank its own synthetic chunk, B sentences per rank and step: weak scaling)."""
     sys.path.insert(0, os.path.join(ROOT, "scripts"))
     import bench_seq
+    held = {}
     r = bench_seq.run(args.config, steps=args.steps, warmup=args.warmup, allreduce=allreduce,
-                      rank=rank, world=world)
+                      rank=rank, world=world, hold=held)
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, engine_outputs(held["eng"], held["nets"], ("o2", "o3")))
+    held.clear()
     peak = MFMA_PEAK_TFLOPS["fp32"]
     res = {"metric": "acoustic frames/sec (train)", "value": round(r["frames_per_s"], 1),
            "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -492,7 +558,7 @@ def seq_main(args, rank, world, allreduce):
     prof = mfma_profile(args.config)
     if prof:
         res["roofline"]["mfma_util"] = prof
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = bench_seq.cpu_baseline(args.config, seconds=args.cpu_seconds)
     print(json.dumps(res), flush=True)
 
@@ -507,6 +573,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--prec", choices=["bf16", "fp32", "bf16x3"], default="bf16")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: its per-launch profile and roofline, the fp32 / "
+                         "bf16x3 entries, the batch sweep, the C3/C4/C5 sequence configurations, "
+                         "the posterior checks against the oracle and the CPU baselines (the "
+                         "--no-* options below drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the timed path holds after its last step (loss, posteriors "
+                         "of the last batch, trained parameters) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-batch-sweep", action="store_true")
@@ -545,9 +619,11 @@ def main():
         return
     from pkc import _lib
     prec = PREC_NAMES[args.prec]
-    head = measure_mlp(prec, args, rank, world, allreduce)
+    full = args.full
+    head = measure_mlp(prec, args, rank, world, allreduce, full=full,
+                       dump=args.dump_outputs if rank == 0 else None)
     extra = {}
-    if rank == 0 and world == 1 and args.prec == "bf16" and not args.no_fp32:
+    if full and rank == 0 and world == 1 and args.prec == "bf16" and not args.no_fp32:
         # the same configuration in fp32 (the reference's precision) and in compensated bf16
         # (bf16 MFMA, fp32-class products): the entries whose posteriors meet north_star's 1e-4,
         # measured the same way, each with its own roofline
@@ -559,7 +635,7 @@ def main():
             extra["fp32_entry"].update(parity_leg(_lib.PREC_FP32, args.batch))
             extra["bf16x3_entry"].update(parity_leg(_lib.PREC_BF16X3, args.batch))
     sweep = {}
-    if rank == 0 and world == 1 and not args.no_batch_sweep:
+    if full and rank == 0 and world == 1 and not args.no_batch_sweep:
         sweep = batch_sweep(prec)
         if args.prec == "bf16" and not args.no_fp32:
             # the reference-precision modes at the large batches: exact fp32 and compensated bf16
@@ -575,7 +651,7 @@ def main():
                     b: parity_leg(_lib.PREC_BF16X3, int(b))["posterior_max_rel_err"] for b in by["fp32"]}
             extra["batch_sweep_by_prec"] = by
     seq = {}
-    if rank == 0 and world == 1 and not args.no_seq_configs:
+    if full and rank == 0 and world == 1 and not args.no_seq_configs:
         # BASELINE configs C3-C5: C3 (the largest single-GPU config) measured like the headline,
         # C4 / C5 informational
         seq["c3"] = seq_entry("c3", max(20, args.steps), 3, False, 0)
@@ -587,7 +663,7 @@ def main():
             torch.cuda.empty_cache()
             seq[c]["bf16_entry"] = seq_entry(c, 8, 2, False, 0, "bf16")
             torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         extra.update(parity_leg(prec, args.batch))
     if rank == 0:
         res = {
@@ -607,17 +683,15 @@ def main():
             "config": {"workload": WORKLOADS["c2"],
                        "global_batch": args.batch * world, "parallelism": "dp%d" % world,
                        "chunk_frames_per_rank": head["chunk_frames_per_rank"]},
-            "roofline": head["roofline"],
-            "launches_per_step": head["launches_per_step"],
             "graph_launches_per_step": head["graph_launches_per_step"],
-            "step_breakdown_us": head["step_breakdown_us"],
-            "batch_sweep_frames_per_s": sweep,
-            "sequence_configs": seq,
             "chunk_prep_s": head["chunk_prep_s"],
             "mean_loss": head["mean_loss"],
         }
+        if full:
+            res.update({k: head[k] for k in ("roofline", "launches_per_step", "step_breakdown_us")})
+            res.update(batch_sweep_frames_per_s=sweep, sequence_configs=seq)
         res.update(extra)
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(args.batch, args.cpu_seconds)
             sys.path.insert(0, os.path.join(ROOT, "scripts"))
             import bench_seq

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 other=${AB_TREE:-_bis_r5}
 : > gpurun_out/c2ab.txt
 for i in 1 2 3; do for t in . "$other"; do
-  (cd "$t" && timeout -k 10 300 python -u bench.py --steps 400 --warmup 40 --no-cpu-baseline \
+  (cd "$t" && timeout -k 10 300 python -u bench.py --full --steps 400 --warmup 40 --no-cpu-baseline \
     --no-batch-sweep --no-fp32 --no-seq-configs) > gpurun_out/c2ab_run.log 2>&1
   rc=$?
   echo "[c2ab $t] rc=$rc"

@@ -145,13 +145,17 @@ def alg_flops_per_row(nets):
     return per_dir_row, head
 
 
-def run(cfg_name, steps, warmup, allreduce=None, rank=0, world=1, prec="fp32", graphs=False):
+def run(cfg_name, steps, warmup, allreduce=None, rank=0, world=1, prec="fp32", graphs=False,
+        hold=None):
     """Times `steps` sentence batches after `warmup` (barrier + synchronize on both sides of the
     timed region; the max over ranks).  frames_per_s is the whole job's: every rank's real frames
     over that time.  graphs: the steps replay per-T captured graphs (Engine.capture), captured in
     an untimed pass over the timed batches first (steady state: every T seen before); the
-    capture pass's rate is reported beside it."""
+    capture pass's rate is reported beside it.  hold: a dict that receives the engine and the
+    nets as they stand after the last timed step ("eng", "nets")."""
     eng, nets, B = build(cfg_name, rank=rank, world=world, prec=prec)
+    if hold is not None:
+        hold.update(eng=eng, nets=nets)
     cap_s = None
     if graphs:
         import pkc.engine as E

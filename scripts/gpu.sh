@@ -7,7 +7,7 @@
 #
 #   tests       pytest -m gpu (all GPU parity tests)          -> gpurun_out/pytest_gpu.log
 #   smoke       __graft_entry__.smoke()                       -> gpurun_out/smoke.log
-#   bench       python bench.py (the driver's default line)   -> gpurun_out/bench.log
+#   bench       python bench.py --full (the headline and every other leg) -> bench.log
 #   bench_prof  the bench under rocprofv3 --kernel-trace --stats + the step timeline
 #                                                             -> gpurun_out/bprof/
 #   pmc         HBM traffic of the dominant launch: FETCH_SIZE and WRITE_SIZE passes
@@ -81,6 +81,7 @@ r_smoke() {
 }
 
 r_bench() {
+  local A="--full $A"      # every leg of the line, not the headline alone
   timeout -k 10 600 python -u bench.py $A > gpurun_out/bench.log 2>&1
   local rc=$?; tail -c 3000 gpurun_out/bench.log; ok $rc bench
 }
