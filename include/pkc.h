@@ -545,6 +545,78 @@ int pkc_dp_comm_init(void** comm_out, int world, const void* id, int rank, int d
 int pkc_dp_allreduce(void* comm, float* buf, int64_t n, void* stream);
 int pkc_dp_comm_destroy(void* comm);
 
+/* ---------------------------------------------------------------------------------------------
+ * Conv1d + max-pool layer of the CNN architecture (neural_networks.py:1934-2033; per layer
+ * :2017-2029  x = drop(act(norm(F.max_pool1d(conv(x), pool))))  over (B, C, L)).  Additive to
+ * ABI 9: new entry points and new structs only.
+ *
+ * pkc_conv1d_fwd (replaces nn.Conv1d + F.max_pool1d, :2021/:2025/:2028): stride 1, no padding,
+ * bias; floor-mode pooling with stride = kernel (the tail L_conv mod pool is dropped).  One
+ * launch: an implicit GEMM on the exact-fp32 MFMA over an LDS strip of x (no im2col tensor), W
+ * read in its native (C_out, C_in * len) layout, bias + max-pool in the epilogue.  Writes the
+ * pooled z (B, C_out, L_out) and, per window, the offset of its first maximum (u8) for the
+ * backward; the pre-pool tensor is never stored.  L_conv = L_in - len + 1, L_out = L_conv / pool.
+ *
+ * pkc_conv1d_bwd (autograd of the same): dz is the gradient of the pooled z.  The un-pooling is
+ * part of the operand load (the value at conv position l is dz[l / pool] where off == l % pool,
+ * else 0).  dx (nullable) = the transposed convolution; dW and dbias are summed per sample group
+ * into partial slabs in `work` (pkc_conv1d_bwd_work_size floats: the same for every B, so a buffer
+ * sized once serves any row count of the layer) and then over the slabs in
+ * slab order: no floating-point atomics, so equal inputs give bit-identical outputs.
+ *
+ * x / dx rows: sample b starts at x + b * ldx (dx + b * lddx), channel-major (C_in, L_in) inside.
+ * pkc_conv1d_ok: 1 when the shape is supported (pool <= 64, len <= 4033).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  int B, C_in, L_in, C_out, len, pool;
+  const float* x; int64_t ldx;              /* (B, C_in, L_in), sample stride ldx floats */
+  const float* W;                           /* (C_out, C_in, len) */
+  const float* bias;                        /* C_out */
+  float* z;                                 /* (B, C_out, L_out): forward output */
+  uint8_t* off;                             /* (B, C_out, L_out): forward output, backward input */
+  const float* dz;                          /* backward: (B, C_out, L_out) */
+  float* dx; int64_t lddx;                  /* backward: (B, C_in, L_in) or NULL */
+  float* dW; float* dbias;                  /* backward: (C_out, C_in, len), (C_out) */
+} pkc_conv1d_args;
+int pkc_conv1d_ok(const pkc_conv1d_args* a);
+int pkc_conv1d_fwd(const pkc_conv1d_args* a, void* stream);
+int64_t pkc_conv1d_bwd_work_size(const pkc_conv1d_args* a);   /* floats; -1: unsupported shape */
+int pkc_conv1d_bwd(const pkc_conv1d_args* a, float* work, void* stream);
+
+/* The rest of the layer over the pooled z (B, C, L), one launch per direction:
+ *   norm PKC_CONV_NORM_LN : the reference's own LayerNorm (neural_networks.py:40-51) over the last
+ *        dimension L of every (b, c) row: gamma[c, l] (z - mean) / (std + eps) + beta[c, l] with
+ *        the unbiased std; ln_stat (B * C, 2) keeps 1 / (std + eps) and std;
+ *   norm PKC_NORM_BN_TRAIN / _EVAL : nn.BatchNorm1d per channel over B * L (:1988-1990, where the
+ *        second positional argument makes eps = L_out: pass that eps), running statistics
+ *        updated in training (unbiased variance);
+ *   norm PKC_NORM_NONE;
+ * then the activation and inverted dropout on the counter-based streams of pkc_dense_fwd (index
+ * = the element's flat (B, C * L) index; keep_in: an injected mask; keep: the mask written /
+ * read by the backward).  out (B, C * L) channel-major and an optional bf16 copy of it.
+ * Backward: g = sum_s gslab[s] (dL/d out); writes dz (B, C, L), dgamma / dbeta ((C, L) for LN,
+ * (C) for BN).  Eval: PKC_NORM_BN_EVAL and drop_p = 0. */
+#define PKC_CONV_NORM_LN 3
+typedef struct {
+  int B, C, L;
+  int norm;                                   /* PKC_NORM_* or PKC_CONV_NORM_LN */
+  const float* z;                             /* (B, C, L) */
+  const float* gamma; const float* beta;      /* BN: (C); LN: (C, L) */
+  float* running_mean; float* running_var;    /* BN: (C) */
+  float momentum, eps;
+  float* save_mean; float* save_invstd;       /* BN training: (C) */
+  float* ln_stat;                             /* LN: (B * C, 2) */
+  int act; float drop_p; uint64_t seed; const int64_t* step_ctr; int64_t stream_id;
+  const uint8_t* keep_in;                     /* optional injected dropout mask (B, C * L) */
+  uint8_t* keep;                              /* (B, C * L); may be NULL when drop_p == 0 */
+  float* xhat;                                /* (B, C, L) normalised z (LN / BN) */
+  float* out; void* out_bf16;                 /* (B, C * L); either may be NULL, not both */
+  int nslab; const float* gslab; int64_t slab_stride;    /* backward: dL/d out slabs */
+  float* dz; float* dgamma; float* dbeta;     /* backward outputs */
+} pkc_conv_post_args;
+int pkc_conv_post_fwd(const pkc_conv_post_args* a, void* stream);
+int pkc_conv_post_bwd(const pkc_conv_post_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,24 @@ class BnBwdEpi(C.Structure):
                 ("act", C.c_int), ("drop_p", C.c_float)]
 
 REG_L1, REG_L2 = 1, 2
+CONV_NORM_LN = 3        # include/pkc.h PKC_CONV_NORM_LN
+
+
+class Conv1dArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("C_in", C.c_int), ("L_in", C.c_int), ("C_out", C.c_int),
+                ("len", C.c_int), ("pool", C.c_int), ("x", vp), ("ldx", i64), ("W", vp), ("bias", vp),
+                ("z", vp), ("off", vp), ("dz", vp), ("dx", vp), ("lddx", i64), ("dW", vp),
+                ("dbias", vp)]
+
+
+class ConvPostArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("C", C.c_int), ("L", C.c_int), ("norm", C.c_int), ("z", vp),
+                ("gamma", vp), ("beta", vp), ("running_mean", vp), ("running_var", vp),
+                ("momentum", C.c_float), ("eps", C.c_float), ("save_mean", vp), ("save_invstd", vp),
+                ("ln_stat", vp), ("act", C.c_int), ("drop_p", C.c_float), ("seed", C.c_uint64),
+                ("step_ctr", vp), ("stream_id", i64), ("keep_in", vp), ("keep", vp), ("xhat", vp),
+                ("out", vp), ("out_bf16", vp), ("nslab", C.c_int), ("gslab", vp),
+                ("slab_stride", i64), ("dz", vp), ("dgamma", vp), ("dbeta", vp)]
 
 
 class RegItem(C.Structure):
@@ -106,6 +124,12 @@ class RegItem(C.Structure):
 
 
 _SIGS = {
+    "pkc_conv1d_ok": (C.c_int, [C.POINTER(Conv1dArgs)]),
+    "pkc_conv1d_fwd": (C.c_int, [C.POINTER(Conv1dArgs), vp]),
+    "pkc_conv1d_bwd_work_size": (i64, [C.POINTER(Conv1dArgs)]),
+    "pkc_conv1d_bwd": (C.c_int, [C.POINTER(Conv1dArgs), vp, vp]),
+    "pkc_conv_post_fwd": (C.c_int, [C.POINTER(ConvPostArgs), vp]),
+    "pkc_conv_post_bwd": (C.c_int, [C.POINTER(ConvPostArgs), vp]),
     "pkc_reg_partial": (C.c_int, [C.c_int, vp, C.c_int, vp, vp]),
     "pkc_reg_finalize": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_float, vp, vp, C.c_int, vp]),
     "pkc_reg_grad": (C.c_int, [C.c_int, vp, C.c_int, vp, vp]),

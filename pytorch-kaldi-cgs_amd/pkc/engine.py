@@ -365,6 +365,81 @@ class NormLayer(Layer):
         return [(self.gamma, "dgamma", None), (self.beta, "dbeta", None)]
 
 
+class ConvNode:
+    """One Conv1d + max-pool layer of a CNN architecture (neural_networks.py:2017-2029) as a graph
+    node.  For its neighbours it is a dense node with no matmul of the engine's own (W is None):
+    N = C_out * L_out, out (rows, N) channel-major, consumers' dX slabs (or a recurrent consumer's)
+    as its output gradient, dX into its producer's slab.  The convolution products are exact fp32
+    in every pkc_prec mode."""
+    rec = False
+    conv = True
+    head = False
+    W = b = mask = Wq = None          # no engine matmul, mask or quantised copy
+    qbits = ibits = reads = 0
+
+    def __init__(self, arch, idx, spec, K):
+        self.arch, self.idx, self.spec = arch, idx, spec
+        self.C_in, self.C_out, self.L_in, self.L_out = (spec["C_in"], spec["C_out"], spec["L_in"],
+                                                        spec["L_out"])
+        self.len, self.pool = spec["len"], spec["pool"]
+        if K != self.C_in * self.L_in:
+            raise ValueError("%s.conv%d: input width %d != C_in * L_in = %d"
+                             % (arch, idx, K, self.C_in * self.L_in))
+        self.K, self.N = K, self.C_out * self.L_out
+        self.name = "%s.conv%d" % (arch, idx)
+        self.act, self.drop = spec["act"], float(spec["drop"])
+        self.bn, self.ln = bool(spec["bn"]), bool(spec["ln"])
+        if self.bn and self.ln:
+            raise NotImplementedError("%s: LayerNorm and BatchNorm both set (the reference then "
+                                      "convolves twice, neural_networks.py:2019-2025)" % self.name)
+        if self.act not in L.ACT:
+            raise NotImplementedError("%s: activation %s on a convolution layer" % (self.name, self.act))
+        self.cW, self.cb = spec["W"], spec["b"]
+        self.gamma, self.beta, self.rm, self.rv = spec["gamma"], spec["beta"], spec["rm"], spec["rv"]
+        self.ln_gamma, self.ln_beta = spec["ln_gamma"], spec["ln_beta"]
+        self.src, self.consumers, self.label_col = None, [], None
+        self.nbt0 = int(spec["nbt"].item()) if spec.get("nbt") is not None else 0
+        self.loss_weight = 0.0
+
+    def params(self):
+        out = [(self.cW, "dW", None), (self.cb, "db", None)]
+        if self.ln:
+            out += [(self.ln_gamma, "dgamma_ln", None), (self.ln_beta, "dbeta_ln", None)]
+        if self.bn:
+            out += [(self.gamma, "dgamma", None), (self.beta, "dbeta", None)]
+        return out
+
+    def quant_of(self, p):
+        return (None, 0)
+
+
+def conv_args(sp, rows, x_ptr, ldx, z, off):
+    """pkc_conv1d_args of a conv_specs() entry over `rows` samples."""
+    a = L.Conv1dArgs(B=rows, C_in=sp["C_in"], L_in=sp["L_in"], C_out=sp["C_out"], len=sp["len"],
+                     pool=sp["pool"], x=x_ptr, ldx=ldx, W=sp["W"].data_ptr(),
+                     bias=sp["b"].data_ptr(), z=z.data_ptr(), off=off.data_ptr())
+    if L.lib().pkc_conv1d_ok(C.byref(a)) != 1:
+        raise NotImplementedError("convolution shape not on the pkc path: %s"
+                                  % L.lib().pkc_last_error().decode())
+    return a
+
+
+def conv_post_args(sp, rows, z, train, out, **kw):
+    """pkc_conv_post_args of a conv_specs() entry (norm / activation / dropout after the pool)."""
+    if sp["ln"]:
+        norm, g, b, eps = L.CONV_NORM_LN, sp["ln_gamma"], sp["ln_beta"], sp.get("ln_eps", 1e-6)
+    elif sp["bn"]:
+        # eps = L_out: neural_networks.py:1988-1990 passes it as BatchNorm1d's second argument
+        norm, g, b, eps = (L.NORM_BN_TRAIN if train else L.NORM_BN_EVAL, sp["gamma"], sp["beta"],
+                           sp["bn_eps"])
+    else:
+        norm, g, b, eps = L.NORM_NONE, None, None, 0.0
+    return L.ConvPostArgs(B=rows, C=sp["C_out"], L=sp["L_out"], norm=norm, z=z.data_ptr(),
+                          gamma=ptr(g), beta=ptr(b), running_mean=sp["rm"].data_ptr(),
+                          running_var=sp["rv"].data_ptr(), momentum=sp.get("bn_momentum", 0.05),
+                          eps=eps, act=L.ACT[sp["act"]], out=out.data_ptr(), **kw)
+
+
 class RecNode:
     """A whole liGRU / LSTM architecture (all its layers) as one graph node."""
     rec = True
@@ -646,6 +721,20 @@ class Engine:
                     prev[1].consumers.append(nl)
                 self.nodes.append(nl)
                 prev = ("node", nl)
+            if hasattr(net, "conv_specs"):       # CNN: one node per Conv1d + max-pool layer
+                if self.sync_bn is not None and any(sp["bn"] for sp in net.conv_specs()):
+                    raise NotImplementedError("sync_bn: %s has a BatchNorm'd convolution layer "
+                                              "(per-rank statistics)" % a)
+                for i, spec in enumerate(net.conv_specs()):
+                    cn = ConvNode(a, i, spec, K)
+                    cn.src = prev
+                    if prev[0] == "node":
+                        prev[1].consumers.append(cn)
+                    self.nodes.append(cn)
+                    prev = ("node", cn)
+                    K = cn.N
+                produced[out] = prev[1]
+                continue
             for i, spec in enumerate(net.layer_specs()):
                 lay = Layer(a, i, spec, K)
                 lay.src = prev
@@ -711,6 +800,9 @@ class Engine:
                     scal[out] = {}
                     continue
                 if op == "cost_gl":
+                    if any(q.dim() > 2 for q in params):
+                        raise NotImplementedError("cost_gl over a convolution weight (torch.chunk "
+                                                  "of a 3-D parameter) is not on the pkc path")
                     if "," not in b:
                         raise NotImplementedError("cost_gl needs an output named loss_gl* "
                                                   "(utils.py:1904-1906)")
@@ -778,6 +870,9 @@ class Engine:
         for n in self.nodes:
             if n.rec:
                 self._alloc_rec(n)
+                continue
+            if getattr(n, "conv", False):
+                self._alloc_conv(n)
                 continue
             N, K = n.N, n.K
             n.scap = self.cap or _splits(M, N, K, MAX_SPLITS_FWD or
@@ -871,6 +966,19 @@ class Engine:
         if self.external:
             self.ext_dx = _f32(M * self.F, dev)   # dL/dx of the caller's input
 
+    def _alloc_conv(self, n):
+        M, dev = self.Mmax, self.dev
+        n.z = _f32(M * n.N, dev)                    # pooled conv output (B, C_out, L_out)
+        n.off = torch.zeros(M * n.N, dtype=torch.uint8, device=dev)   # first-max offset per window
+        n.out = _f32(M * n.N, dev)
+        n.xhat = _f32(M * n.N, dev) if (n.bn or n.ln) else None
+        n.keep = torch.zeros(M * n.N, dtype=torch.uint8, device=dev) if n.drop > 0 else None
+        n.save_mean, n.save_invstd = _f32(n.C_out, dev), _f32(n.C_out, dev)
+        n.ln_stat = _f32(2 * M * n.C_out, dev) if n.ln else None
+        n.dz = _f32(M * n.N, dev)
+        a = conv_args(n.spec, M, None, n.K, n.z, n.off)
+        n.work = _f32(L.lib().pkc_conv1d_bwd_work_size(C.byref(a)), dev)
+
     def _dw_splits(self, N, K):
         """K-splits of a dense layer's dW = dz^T X (contraction over the M batch rows): enough
         128x128 tiles x splits for ~256 workgroups at large batches, at most 4, >= 256 rows each."""
@@ -906,6 +1014,9 @@ class Engine:
         if any(n.src[0] == "fea" for n in mm):
             self.x_h = torch.zeros(M * self.F, dtype=bf, device=dev)
         keep_f32 = os.environ.get("PKC_F32_OUT", "0") != "0"
+        for n in self.nodes:                # a conv node's output for its bf16 consumer matmuls
+            if getattr(n, "conv", False) and any(c in mm for c in n.consumers):
+                n.out_h = torch.zeros(M * n.N, dtype=bf, device=dev)
         for n in mm:
             n.W_h = torch.zeros(n.W.numel(), dtype=bf, device=dev)
             if not n.head and any(c in mm for c in n.consumers):
@@ -1869,6 +1980,10 @@ class Engine:
                 self._rec_fwd(n, s, train)
                 i += 1
                 continue
+            if getattr(n, "conv", False):
+                self._conv_fwd(n, s, train)
+                i += 1
+                continue
             if n.W is None:
                 self._fwd_epilogue(n, s, train)
                 i += 1
@@ -1898,6 +2013,58 @@ class Engine:
                     "pkc_loss_finalize", self.n_loss_terms, ptr(self.loss_ptrs), ptr(self.loss_w),
                     self.M, ptr(self.err_layer.row_err), ptr(self.loss_out), ptr(self.loss_acc),
                     None if self.seq else ptr(self.ctr), s)
+
+    def _conv_fwd(self, n, s, train):
+        """A conv node's two forward launches: convolution + bias + max-pool, then norm /
+        activation / dropout."""
+        M, sp = self.M, n.spec
+        x_ptr, ldx = self._src(n)
+        a = conv_args(sp, M, x_ptr, ldx, n.z, n.off)
+        Lc = n.L_in - n.len + 1
+        self._k("conv1d_fwd %s" % n.name, 2.0 * M * n.C_out * Lc * n.C_in * n.len,
+                4.0 * (M * n.K + n.cW.numel() + M * n.N) + M * n.N, "pkc_conv1d_fwd", C.byref(a), s)
+        keep_in = self.drop_keep_in.get(n.name)
+        out_h = getattr(n, "out_h", None)
+        pa = conv_post_args(
+            sp, M, n.z, train, n.out, save_mean=n.save_mean.data_ptr(),
+            save_invstd=n.save_invstd.data_ptr(), ln_stat=ptr(n.ln_stat),
+            drop_p=n.drop if train else 0.0, seed=self.seed, step_ctr=self.ctr.data_ptr(),
+            stream_id=zlib.crc32(n.name.encode()), keep_in=ptr(keep_in),
+            keep=n.keep.data_ptr() if (n.keep is not None and train) else None, xhat=ptr(n.xhat),
+            out_bf16=ptr(out_h))
+        self._k("conv_post_fwd %s" % n.name, 0, 4.0 * M * n.N * 3, "pkc_conv_post_fwd", C.byref(pa), s)
+
+    def _conv_bwd(self, n, s):
+        """A conv node's backward: dropout / activation / norm over its output gradient (the
+        consumers' dX slabs, a recurrent consumer's, or the caller's), then dX / dW / dbias."""
+        M, sp = self.M, n.spec
+        gs = getattr(n, "gsrc", None)
+        if gs is not None:
+            g_ptr, g_ns, g_st = gs[0].data_ptr(), gs[1], gs[2]
+        else:
+            g_ptr, g_ns, g_st = n.gslab.data_ptr(), n.sb, M * n.N
+        dg, db = (n.dgamma_ln, n.dbeta_ln) if n.ln else (n.dgamma, n.dbeta) if n.bn else (None, None)
+        pa = conv_post_args(
+            sp, M, n.z, True, n.out, save_invstd=n.save_invstd.data_ptr(), ln_stat=ptr(n.ln_stat),
+            drop_p=n.drop, keep=ptr(n.keep), xhat=ptr(n.xhat), nslab=g_ns, gslab=g_ptr,
+            slab_stride=g_st, dz=n.dz.data_ptr(), dgamma=ptr(dg), dbeta=ptr(db))
+        self._k("conv_post_bwd %s" % n.name, 0, 4.0 * M * n.N * (g_ns + 3), "pkc_conv_post_bwd",
+                C.byref(pa), s)
+        x_ptr, ldx = self._src(n)
+        a = conv_args(sp, M, x_ptr, ldx, n.z, n.off)
+        a.dz, a.dW, a.dbias = n.dz.data_ptr(), n.dW.data_ptr(), n.db.data_ptr()
+        flops = 2.0 * M * n.C_out * (n.L_in - n.len + 1) * n.C_in * n.len
+        if n.src[0] == "node" and self.needs_grad[n.src[1]]:
+            P = n.src[1]
+            a.dx, a.lddx = self._norm_dx(n).data_ptr(), n.K
+            P.bnb_now = False
+            flops *= 2
+        elif n.src[0] == "fea" and self.want_dx:       # external mode: dL/dx of the caller's input
+            a.dx, a.lddx = self.ext_dx.data_ptr() + 4 * n.src[1], self.F
+            flops *= 2
+        self._k("conv1d_bwd %s" % n.name, flops,
+                4.0 * (2 * M * n.K + 2 * n.cW.numel() + M * n.N + n.work.numel()) + M * n.N,
+                "pkc_conv1d_bwd", C.byref(a), ptr(n.work), s)
 
     def _loss_op(self):
         """The loss reduction (and batch-counter advance) as an operation of the first backward
@@ -2356,7 +2523,10 @@ class Engine:
                 continue
             if not n.head:
                 flush()
-            self._dense_bwd_pre(n, s)
+            if getattr(n, "conv", False):
+                self._conv_bwd(n, s)
+            else:
+                self._dense_bwd_pre(n, s)
             pend += self._bwd_problems(n)
             pend_nodes.append(n)
             lag = 1
@@ -2863,6 +3033,36 @@ def torch_optimizer(params, o):
     raise NotImplementedError("arch_opt=%s" % kind)
 
 
+def _input_norm_bufs(norms, max_rows, inp_dim, dev):
+    """Work buffers of the forward runners' input LayerNorm / BatchNorm (one set per norm)."""
+    return [dict(y=_f32(max_rows * inp_dim, dev), xh=_f32(max_rows * inp_dim, dev),
+                 st=_f32(2 * max_rows, dev), sm=_f32(inp_dim, dev), si=_f32(inp_dim, dev),
+                 work=_f32(L.lib().pkc_dense_work_size(max_rows, inp_dim), dev))
+            for _ in norms]
+
+
+def _run_input_norms(norms, nbufs, cur, cld, K0, M, train, s):
+    """ln0 then bn0 of a forward runner over the (M, K0) matrix at address cur (row stride cld);
+    returns the address of the normalised matrix (cur itself without norms)."""
+    for ns, nb in zip(norms, nbufs):
+        if cld != K0:
+            raise NotImplementedError("input normalisation of a strided feature stream")
+        if ns["kind"] == "ln":
+            call("pkc_layernorm_fwd", M, K0, 1, C.c_void_p(cur), 0, None, ptr(ns["gamma"]),
+                 ptr(ns["beta"]), C.c_float(1e-6), ptr(nb["y"]), ptr(nb["xh"]), ptr(nb["st"]), s)
+        else:
+            a = L.DenseFwdArgs(
+                M=M, N=K0, nslab=1, zslab=cur, slab_stride=0, bias=None,
+                norm=L.NORM_BN_TRAIN if train else L.NORM_BN_EVAL, gamma=ns["gamma"].data_ptr(),
+                beta=ns["beta"].data_ptr(), running_mean=ns["rm"].data_ptr(),
+                running_var=ns["rv"].data_ptr(), momentum=0.05, eps=1e-5,
+                save_mean=nb["sm"].data_ptr(), save_invstd=nb["si"].data_ptr(), act=0,
+                xhat=nb["xh"].data_ptr(), out=nb["y"].data_ptr(), count_n=0)
+            call("pkc_dense_fwd", C.byref(a), ptr(nb["work"]), s)
+        cur = nb["y"].data_ptr()
+    return cur
+
+
 class ModuleRunner:
     """Forward of one MLP module on the pkc kernels for any row count <= max_rows (MLP.forward for
     stand-alone calls, and the per-utterance forward of run_nn's forward mode)."""
@@ -2872,11 +3072,7 @@ class ModuleRunner:
         self.net, self.rows, self.dev = net, max_rows, next(net.parameters()).device
         self.specs = net.layer_specs()
         self.norms = net.input_norm_specs() if hasattr(net, "input_norm_specs") else []
-        self.nbufs = [dict(y=_f32(max_rows * inp_dim, self.dev), xh=_f32(max_rows * inp_dim, self.dev),
-                           st=_f32(2 * max_rows, self.dev), sm=_f32(inp_dim, self.dev),
-                           si=_f32(inp_dim, self.dev),
-                           work=_f32(L.lib().pkc_dense_work_size(max_rows, inp_dim), self.dev))
-                      for _ in self.norms]
+        self.nbufs = _input_norm_bufs(self.norms, max_rows, inp_dim, self.dev)
         self.bufs = []
         K = inp_dim
         for sp in self.specs:
@@ -2935,23 +3131,7 @@ class ModuleRunner:
         s = Engine._stream()
         cur, cld = x_ptr, ld
         self.input_version = None
-        for ns, nb in zip(self.norms, self.nbufs):       # input LayerNorm / BatchNorm
-            K0 = self.bufs[0]["K"]
-            if cld != K0:
-                raise NotImplementedError("input normalisation of a strided feature stream")
-            if ns["kind"] == "ln":
-                call("pkc_layernorm_fwd", M, K0, 1, C.c_void_p(cur), 0, None, ptr(ns["gamma"]),
-                     ptr(ns["beta"]), C.c_float(1e-6), ptr(nb["y"]), ptr(nb["xh"]), ptr(nb["st"]), s)
-            else:
-                a = L.DenseFwdArgs(
-                    M=M, N=K0, nslab=1, zslab=cur, slab_stride=0, bias=None,
-                    norm=L.NORM_BN_TRAIN if train else L.NORM_BN_EVAL, gamma=ns["gamma"].data_ptr(),
-                    beta=ns["beta"].data_ptr(), running_mean=ns["rm"].data_ptr(),
-                    running_var=ns["rv"].data_ptr(), momentum=0.05, eps=1e-5,
-                    save_mean=nb["sm"].data_ptr(), save_invstd=nb["si"].data_ptr(), act=0,
-                    xhat=nb["xh"].data_ptr(), out=nb["y"].data_ptr(), count_n=0)
-                call("pkc_dense_fwd", C.byref(a), ptr(nb["work"]), s)
-            cur = nb["y"].data_ptr()
+        cur = _run_input_norms(self.norms, self.nbufs, cur, cld, self.bufs[0]["K"], M, train, s)
         for li, (sp, b) in enumerate(zip(self.specs, self.bufs)):
             N, K = b["N"], b["K"]
             if sp["inp_quant"]:
@@ -2998,6 +3178,47 @@ class ModuleRunner:
         return self.run(x.data_ptr(), x.shape[1], x.shape[0], train).clone()
 
 
+class ConvRunner:
+    """Forward of one CNN module on the pkc kernels for any row count <= max_rows (run_nn's forward
+    mode): the ModuleRunner interface."""
+
+    def __init__(self, net, max_rows, inp_dim):
+        net.check_supported()
+        self.net, self.rows, self.dev = net, max_rows, next(net.parameters()).device
+        self.specs = net.conv_specs()
+        self.norms = net.input_norm_specs()
+        self.nbufs = _input_norm_bufs(self.norms, max_rows, inp_dim, self.dev)
+        self.inp_dim = inp_dim
+        self.bufs = []
+        for sp in self.specs:
+            N = sp["C_out"] * sp["L_out"]
+            self.bufs.append(dict(
+                N=N, z=_f32(max_rows * N, self.dev), out=_f32(max_rows * N, self.dev),
+                off=torch.zeros(max_rows * N, dtype=torch.uint8, device=self.dev),
+                xhat=_f32(max_rows * N, self.dev), sm=_f32(sp["C_out"], self.dev),
+                si=_f32(sp["C_out"], self.dev), st=_f32(2 * max_rows * sp["C_out"], self.dev)))
+        self.input_version = None
+
+    def run(self, x_ptr, ld, M, train=False, log_prior=None):
+        assert M <= self.rows
+        s = Engine._stream()
+        cur, cld = x_ptr, ld
+        cur = _run_input_norms(self.norms, self.nbufs, cur, cld, self.inp_dim, M, train, s)
+        for sp, b in zip(self.specs, self.bufs):
+            a = conv_args(sp, M, cur, cld, b["z"], b["off"])
+            call("pkc_conv1d_fwd", C.byref(a), s)
+            pa = conv_post_args(sp, M, b["z"], train, b["out"], save_mean=b["sm"].data_ptr(),
+                                save_invstd=b["si"].data_ptr(), ln_stat=b["st"].data_ptr(),
+                                drop_p=0.0, xhat=b["xhat"].data_ptr())
+            call("pkc_conv_post_fwd", C.byref(pa), s)
+            cur, cld = b["out"].data_ptr(), b["N"]
+        return self.bufs[-1]["out"][:M * self.bufs[-1]["N"]].view(M, -1)
+
+    def forward(self, x, train=False):
+        x = x.contiguous().float()
+        return self.run(x.data_ptr(), x.shape[1], x.shape[0], train).clone()
+
+
 class ForwardRunner:
     """run_nn forward mode (core.py:134-145, 234-249) for feed-forward models: one utterance per
     batch, BatchNorm with running statistics, no dropout, posteriors normalised by the log prior."""
@@ -3011,7 +3232,8 @@ class ForwardRunner:
         dims = {k: c1 - c0 for k, (c0, c1) in fea_cols.items()}
         for out, op, a, b in lines:
             if op == "compute":
-                self.runners[a] = ModuleRunner(nets[a], max_rows, dims[b])
+                runner = ConvRunner if hasattr(nets[a], "conv_specs") else ModuleRunner
+                self.runners[a] = runner(nets[a], max_rows, dims[b])
                 dims[out] = nets[a].out_dim
         self.priors_dev = {}
 

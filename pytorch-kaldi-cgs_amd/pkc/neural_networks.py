@@ -284,6 +284,101 @@ class MLP(_PatternSet, nn.Module):
         return arch_forward(self, x)
 
 
+class CNN(nn.Module):
+    """neural_networks.py:1934-2033 (options per proto/CNN.proto): Conv1d + max-pool layers over
+    the (B, 1, inp_dim) input, x = drop(act(norm(max_pool1d(conv(x), pool)))) per layer, output
+    (B, C_out * L_out) channel-major.  Parameters conv.i, bn.i, ln.i (both norm holders are always
+    registered, as the reference does); per layer only the Conv1d draws from the RNG."""
+
+    seq_model = False
+
+    def __init__(self, options, inp_dim):
+        super().__init__()
+        o = options
+        self.input_dim = inp_dim
+        self.cnn_N_filt = _lst(o, "cnn_N_filt", int)
+        self.cnn_len_filt = _lst(o, "cnn_len_filt", int)
+        self.cnn_max_pool_len = _lst(o, "cnn_max_pool_len", int)
+        self.cnn_act = _lst(o, "cnn_act")
+        self.cnn_drop = _lst(o, "cnn_drop", float)
+        self.cnn_use_laynorm = _lst(o, "cnn_use_laynorm", strtobool)
+        self.cnn_use_batchnorm = _lst(o, "cnn_use_batchnorm", strtobool)
+        self.cnn_use_laynorm_inp = strtobool(o["cnn_use_laynorm_inp"])
+        self.cnn_use_batchnorm_inp = strtobool(o["cnn_use_batchnorm_inp"])
+        self.to_do = o.get("to_do", "train")
+        # core.run_nn / utils read these on every architecture; the reference CNN has no CGS hooks
+        self.prune = False
+        self.guided_hcgs = False
+        self.apply_guided_hcgs = False
+        self.if_pattern = False
+        self.skip_regularization = strtobool(o.get("skip_regularization", "False"))
+        # the reference CNN has no masks, quantisation or pruning: such keys are refused, not ignored
+        self._cgs_keys = [k for k in ("cnn_hcgs", "cnn_quant", "cnn_quant_inp", "cnn_prune",
+                                      "guided_hcgs", "apply_guided_hcgs", "if_pattern")
+                          if strtobool(o.get(k, "False"))]
+        self.N_cnn_lay = len(self.cnn_N_filt)
+        self.conv, self.bn, self.ln = nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
+        if self.cnn_use_laynorm_inp:
+            self.ln0 = LayerNorm(inp_dim)
+        if self.cnn_use_batchnorm_inp:
+            self.bn0 = nn.BatchNorm1d(inp_dim, momentum=0.05)
+        cur, cin = inp_dim, 1
+        self.L_in, self.L_out = [], []
+        for i, n in enumerate(self.cnn_N_filt):
+            lout = int((cur - self.cnn_len_filt[i] + 1) / self.cnn_max_pool_len[i])
+            self.ln.append(LayerNorm([n, lout]))
+            # neural_networks.py:1988-1990: nn.BatchNorm1d(N_filt, <L_out>, momentum=0.05) puts
+            # L_out into the second positional parameter, eps: reproduced (eps = L_out)
+            self.bn.append(nn.BatchNorm1d(n, eps=lout, momentum=0.05))
+            self.conv.append(nn.Conv1d(cin, n, self.cnn_len_filt[i]))   # the only RNG draws
+            self.L_in.append(cur)
+            self.L_out.append(lout)
+            cur, cin = lout, n
+        self.out_dim = cur * self.cnn_N_filt[-1]
+
+    def prune_parameters(self):
+        raise NotImplementedError("the reference CNN has no prune hook")
+
+    def forward(self, x):
+        """(B, F) -> (B, out_dim) on the pkc kernels, trainable under autograd (pkc.plugin)."""
+        return arch_forward(self, x)
+
+    def check_supported(self):
+        if self._cgs_keys:
+            raise NotImplementedError("CNN: %s (the reference CNN has no weight masks, "
+                                      "quantisation or pruning)" % ", ".join(self._cgs_keys))
+        for i in range(self.N_cnn_lay):
+            if self.cnn_use_laynorm[i] and self.cnn_use_batchnorm[i]:
+                raise NotImplementedError(
+                    "CNN layer %d has cnn_use_laynorm and cnn_use_batchnorm both set: the "
+                    "reference then applies the convolution twice (neural_networks.py:2019-2025)"
+                    % i)
+            if self.cnn_act[i] == "softmax":
+                raise NotImplementedError("CNN layer %d: softmax on a convolution layer" % i)
+            if self.L_out[i] < 1:
+                raise ValueError("CNN layer %d has no output (L_out = %d)" % (i, self.L_out[i]))
+
+    def input_norm_specs(self):
+        return _input_norm_specs(self, self.cnn_use_laynorm_inp, self.cnn_use_batchnorm_inp)
+
+    def conv_specs(self):
+        """Per-layer description consumed by pkc.engine (ConvNode)."""
+        specs = []
+        for i, n in enumerate(self.cnn_N_filt):
+            specs.append(dict(C_in=1 if i == 0 else self.cnn_N_filt[i - 1], C_out=n,
+                              L_in=self.L_in[i], L_out=self.L_out[i], len=self.cnn_len_filt[i],
+                              pool=self.cnn_max_pool_len[i], act=self.cnn_act[i],
+                              drop=self.cnn_drop[i], bn=bool(self.cnn_use_batchnorm[i]),
+                              ln=bool(self.cnn_use_laynorm[i]), W=self.conv[i].weight,
+                              b=self.conv[i].bias, gamma=self.bn[i].weight, beta=self.bn[i].bias,
+                              rm=self.bn[i].running_mean, rv=self.bn[i].running_var,
+                              nbt=self.bn[i].num_batches_tracked, bn_eps=float(self.bn[i].eps),
+                              bn_momentum=float(self.bn[i].momentum),
+                              ln_gamma=self.ln[i].gamma, ln_beta=self.ln[i].beta,
+                              ln_eps=float(self.ln[i].eps)))
+        return specs
+
+
 class liGRU(nn.Module):
     """neural_networks.py:1429-1599 (options per proto/liGRU.proto).  Parameters: wh, wz (input
     Linear), uh, uz (recurrent Linear, no bias), bn_wh, bn_wz, ln; same names and init draws."""
