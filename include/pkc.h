@@ -617,6 +617,44 @@ typedef struct {
 int pkc_conv_post_fwd(const pkc_conv_post_args* a, void* stream);
 int pkc_conv_post_bwd(const pkc_conv_post_args* a, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sinc filter bank: layer 0 of the SincNet architecture (neural_networks.py:2036-2143; SincConv
+ * :2146-2283).  Its convolution weights are N band-pass filters of K taps generated before every
+ * forward from two learned vectors low_hz_ and band_hz_ (N each):
+ *   low = min_low_hz / sr + |low_hz_|,  high = low + min_band_hz / sr + |band_hz_|,
+ *   lp(f)[k] = 2 f sinc(2 pi (f n_[k]) sr)   (sin(x) / x on the left half, 1 at the centre, the
+ *   right half the flip of the left),  bp = lp(high) - lp(low),  filters = bp / max_k bp * window.
+ * n_ and window (K floats each) are computed by the caller with the reference's own expressions
+ * (:2226-2232), so their rounding is the reference's.  Additive to ABI 9.
+ *
+ * pkc_sinc_filters_fwd: filters (N, K) fp32 in the reference's operation order with the precise
+ * sinf: the (C_out, 1, K) weight pkc_conv1d_fwd reads (C_in = 1, len = K, a zero bias).  Per filter
+ * it also writes max_ and the index of the first maximum (torch.max's; always in the left half or
+ * the centre, since the right half repeats the left).
+ *
+ * pkc_sinc_filters_bwd: dW (N, K), the filters' gradient as pkc_conv1d_bwd writes it, -> dlow and
+ * dband (N): through the window, the division by the maximum (whose index is the forward's), the
+ * flip and |.| (gradient 0 at exactly 0).  It re-evaluates the formula in fp64 from the two
+ * parameters, so max_ is an output of the forward only.  One workgroup per filter, sums in a fixed
+ * order, no atomics: equal inputs give bit-identical outputs.
+ *
+ * pkc_sinc_ok: 1 when the shape is supported: K odd, 1 <= K <= 4033 (pkc_conv1d's longest
+ * filter), 1 <= N <= 65535, sr > 0, min_low_hz >= 0, min_band_hz >= 0.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  int N, K;
+  const float* low_hz; const float* band_hz;  /* (N): the parameters low_hz_, band_hz_ */
+  const float* n_; const float* window;       /* (K): SincConv.n_, SincConv.window_ */
+  float sr, min_low_hz, min_band_hz;
+  float* filters;                             /* (N, K): forward output */
+  float* max_; int* max_idx;                  /* (N): forward outputs; max_idx backward input */
+  const float* dW;                            /* backward: (N, K) */
+  float* dlow; float* dband;                  /* backward outputs: (N) */
+} pkc_sinc_args;
+int pkc_sinc_ok(const pkc_sinc_args* a);
+int pkc_sinc_filters_fwd(const pkc_sinc_args* a, void* stream);
+int pkc_sinc_filters_bwd(const pkc_sinc_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,13 @@ class ConvPostArgs(C.Structure):
                 ("slab_stride", i64), ("dz", vp), ("dgamma", vp), ("dbeta", vp)]
 
 
+class SincArgs(C.Structure):
+    _fields_ = [("N", C.c_int), ("K", C.c_int), ("low_hz", vp), ("band_hz", vp), ("n_", vp),
+                ("window", vp), ("sr", C.c_float), ("min_low_hz", C.c_float),
+                ("min_band_hz", C.c_float), ("filters", vp), ("max_", vp), ("max_idx", vp),
+                ("dW", vp), ("dlow", vp), ("dband", vp)]
+
+
 class RegItem(C.Structure):
     _fields_ = [("p", vp), ("g", vp), ("ld", i64), ("r0", C.c_int), ("r1", C.c_int),
                 ("c0", C.c_int), ("c1", C.c_int), ("block", C.c_int), ("assign", C.c_int)]
@@ -130,6 +137,9 @@ _SIGS = {
     "pkc_conv1d_bwd": (C.c_int, [C.POINTER(Conv1dArgs), vp, vp]),
     "pkc_conv_post_fwd": (C.c_int, [C.POINTER(ConvPostArgs), vp]),
     "pkc_conv_post_bwd": (C.c_int, [C.POINTER(ConvPostArgs), vp]),
+    "pkc_sinc_ok": (C.c_int, [C.POINTER(SincArgs)]),
+    "pkc_sinc_filters_fwd": (C.c_int, [C.POINTER(SincArgs), vp]),
+    "pkc_sinc_filters_bwd": (C.c_int, [C.POINTER(SincArgs), vp]),
     "pkc_reg_partial": (C.c_int, [C.c_int, vp, C.c_int, vp, vp]),
     "pkc_reg_finalize": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_float, vp, vp, C.c_int, vp]),
     "pkc_reg_grad": (C.c_int, [C.c_int, vp, C.c_int, vp, vp]),

@@ -366,11 +366,13 @@ class NormLayer(Layer):
 
 
 class ConvNode:
-    """One Conv1d + max-pool layer of a CNN architecture (neural_networks.py:2017-2029) as a graph
-    node.  For its neighbours it is a dense node with no matmul of the engine's own (W is None):
-    N = C_out * L_out, out (rows, N) channel-major, consumers' dX slabs (or a recurrent consumer's)
-    as its output gradient, dX into its producer's slab.  The convolution products are exact fp32
-    in every pkc_prec mode."""
+    """One Conv1d + max-pool layer of a CNN / SincNet architecture (neural_networks.py:2017-2029,
+    :2127-2139) as a graph node.  For its neighbours it is a dense node with no matmul of the
+    engine's own (W is None): N = C_out * L_out, out (rows, N) channel-major, consumers' dX slabs
+    (or a recurrent consumer's) as its output gradient, dX into its producer's slab.  The
+    convolution products are exact fp32 in every pkc_prec mode.  A sinc layer (SincNet's layer 0)
+    convolves with an engine-owned filter buffer regenerated from low_hz_ / band_hz_ at the start
+    of every forward; those two are its parameters, its dW a work buffer."""
     rec = False
     conv = True
     head = False
@@ -394,6 +396,9 @@ class ConvNode:
                                       "convolves twice, neural_networks.py:2019-2025)" % self.name)
         if self.act not in L.ACT:
             raise NotImplementedError("%s: activation %s on a convolution layer" % (self.name, self.act))
+        self.sinc = spec.get("sinc")
+        if self.sinc is not None:
+            sinc_bind(spec)
         self.cW, self.cb = spec["W"], spec["b"]
         self.gamma, self.beta, self.rm, self.rv = spec["gamma"], spec["beta"], spec["rm"], spec["rv"]
         self.ln_gamma, self.ln_beta = spec["ln_gamma"], spec["ln_beta"]
@@ -402,7 +407,10 @@ class ConvNode:
         self.loss_weight = 0.0
 
     def params(self):
-        out = [(self.cW, "dW", None), (self.cb, "db", None)]
+        if self.sinc is not None:
+            out = [(self.sinc["low"], "dlow", None), (self.sinc["band"], "dband", None)]
+        else:
+            out = [(self.cW, "dW", None), (self.cb, "db", None)]
         if self.ln:
             out += [(self.ln_gamma, "dgamma_ln", None), (self.ln_beta, "dbeta_ln", None)]
         if self.bn:
@@ -420,6 +428,33 @@ def conv_args(sp, rows, x_ptr, ldx, z, off):
                      bias=sp["b"].data_ptr(), z=z.data_ptr(), off=off.data_ptr())
     if L.lib().pkc_conv1d_ok(C.byref(a)) != 1:
         raise NotImplementedError("convolution shape not on the pkc path: %s"
+                                  % L.lib().pkc_last_error().decode())
+    return a
+
+
+def sinc_bind(sp):
+    """Buffers of a sinc layer's conv_specs() entry: the generated filters as its W, a zero bias
+    (SincConv has none), the maximum and its index per filter, n_ and window_ on the device."""
+    sn = sp["sinc"]
+    dev, N, K = sn["low"].device, sp["C_out"], sp["len"]
+    sp["W"], sp["b"] = _f32(N * K, dev).view(N, 1, K), _f32(N, dev)
+    sn["max_"], sn["idx"] = _f32(N, dev), torch.zeros(N, dtype=torch.int32, device=dev)
+    sn["n_dev"] = sn["n_"].detach().reshape(-1).to(dev, torch.float32).contiguous()
+    sn["window_dev"] = sn["window"].detach().reshape(-1).to(dev, torch.float32).contiguous()
+    sinc_args(sp)
+
+
+def sinc_args(sp, **kw):
+    """pkc_sinc_args of a bound sinc layer."""
+    sn = sp["sinc"]
+    a = L.SincArgs(N=sp["C_out"], K=sp["len"], low_hz=sn["low"].data_ptr(),
+                   band_hz=sn["band"].data_ptr(), n_=sn["n_dev"].data_ptr(),
+                   window=sn["window_dev"].data_ptr(), sr=sn["sr"], min_low_hz=sn["min_low_hz"],
+                   min_band_hz=sn["min_band_hz"], filters=sp["W"].data_ptr(),
+                   max_=sn["max_"].data_ptr(), max_idx=sn["idx"].data_ptr(), **kw)
+    if (sn["n_dev"].numel() != a.K or sn["window_dev"].numel() != a.K
+            or L.lib().pkc_sinc_ok(C.byref(a)) != 1):
+        raise NotImplementedError("sinc filter bank not on the pkc path: %s"
                                   % L.lib().pkc_last_error().decode())
     return a
 
@@ -800,9 +835,12 @@ class Engine:
                     scal[out] = {}
                     continue
                 if op == "cost_gl":
-                    if any(q.dim() > 2 for q in params):
-                        raise NotImplementedError("cost_gl over a convolution weight (torch.chunk "
-                                                  "of a 3-D parameter) is not on the pkc path")
+                    if any(q.dim() > 2 for q in params) or any(
+                            hasattr(net, "conv_specs") for net in self.nets.values()
+                            if not getattr(net, "skip_regularization", False)):
+                        raise NotImplementedError("cost_gl over a convolution architecture "
+                                                  "(torch.chunk of a 3-D parameter) is not on the "
+                                                  "pkc path")
                     if "," not in b:
                         raise NotImplementedError("cost_gl needs an output named loss_gl* "
                                                   "(utils.py:1904-1906)")
@@ -976,6 +1014,8 @@ class Engine:
         n.save_mean, n.save_invstd = _f32(n.C_out, dev), _f32(n.C_out, dev)
         n.ln_stat = _f32(2 * M * n.C_out, dev) if n.ln else None
         n.dz = _f32(M * n.N, dev)
+        if n.sinc is not None:                      # the filters' gradient and a discarded dbias
+            n.dW, n.db = _f32(n.cW.numel(), dev), _f32(n.C_out, dev)
         a = conv_args(n.spec, M, None, n.K, n.z, n.off)
         n.work = _f32(L.lib().pkc_conv1d_bwd_work_size(C.byref(a)), dev)
 
@@ -2018,6 +2058,10 @@ class Engine:
         """A conv node's two forward launches: convolution + bias + max-pool, then norm /
         activation / dropout."""
         M, sp = self.M, n.spec
+        if n.sinc is not None:          # this step's filters, from the parameters as they are now
+            sa = sinc_args(sp)
+            self._k("sinc_filters_fwd %s" % n.name, 0, 4.0 * n.cW.numel(), "pkc_sinc_filters_fwd",
+                    C.byref(sa), s)
         x_ptr, ldx = self._src(n)
         a = conv_args(sp, M, x_ptr, ldx, n.z, n.off)
         Lc = n.L_in - n.len + 1
@@ -2065,6 +2109,10 @@ class Engine:
         self._k("conv1d_bwd %s" % n.name, flops,
                 4.0 * (2 * M * n.K + 2 * n.cW.numel() + M * n.N + n.work.numel()) + M * n.N,
                 "pkc_conv1d_bwd", C.byref(a), ptr(n.work), s)
+        if n.sinc is not None:          # the filters' gradient through the filter-bank formula
+            sa = sinc_args(sp, dW=n.dW.data_ptr(), dlow=n.dlow.data_ptr(), dband=n.dband.data_ptr())
+            self._k("sinc_filters_bwd %s" % n.name, 0, 4.0 * n.cW.numel(), "pkc_sinc_filters_bwd",
+                    C.byref(sa), s)
 
     def _loss_op(self):
         """The loss reduction (and batch-counter advance) as an operation of the first backward
@@ -3179,8 +3227,9 @@ class ModuleRunner:
 
 
 class ConvRunner:
-    """Forward of one CNN module on the pkc kernels for any row count <= max_rows (run_nn's forward
-    mode): the ModuleRunner interface."""
+    """Forward of one CNN / SincNet module on the pkc kernels for any row count <= max_rows
+    (run_nn's forward mode): the ModuleRunner interface.  A sinc layer's filters are generated once
+    per call."""
 
     def __init__(self, net, max_rows, inp_dim):
         net.check_supported()
@@ -3191,6 +3240,8 @@ class ConvRunner:
         self.inp_dim = inp_dim
         self.bufs = []
         for sp in self.specs:
+            if sp.get("sinc") is not None:
+                sinc_bind(sp)
             N = sp["C_out"] * sp["L_out"]
             self.bufs.append(dict(
                 N=N, z=_f32(max_rows * N, self.dev), out=_f32(max_rows * N, self.dev),
@@ -3205,6 +3256,8 @@ class ConvRunner:
         cur, cld = x_ptr, ld
         cur = _run_input_norms(self.norms, self.nbufs, cur, cld, self.inp_dim, M, train, s)
         for sp, b in zip(self.specs, self.bufs):
+            if sp.get("sinc") is not None:          # the filters of the current parameters
+                call("pkc_sinc_filters_fwd", C.byref(sinc_args(sp)), s)
             a = conv_args(sp, M, cur, cld, b["z"], b["off"])
             call("pkc_conv1d_fwd", C.byref(a), s)
             pa = conv_post_args(sp, M, b["z"], train, b["out"], save_mean=b["sm"].data_ptr(),

@@ -284,98 +284,194 @@ class MLP(_PatternSet, nn.Module):
         return arch_forward(self, x)
 
 
-class CNN(nn.Module):
-    """neural_networks.py:1934-2033 (options per proto/CNN.proto): Conv1d + max-pool layers over
-    the (B, 1, inp_dim) input, x = drop(act(norm(max_pool1d(conv(x), pool)))) per layer, output
-    (B, C_out * L_out) channel-major.  Parameters conv.i, bn.i, ln.i (both norm holders are always
-    registered, as the reference does); per layer only the Conv1d draws from the RNG."""
+class _ConvArch(nn.Module):
+    """What CNN (neural_networks.py:1934-2033) and SincNet (:2036-2143) share: Conv1d + max-pool
+    layers over the (B, 1, inp_dim) input, x = drop(act(norm(max_pool1d(conv(x), pool)))) per
+    layer, output (B, C_out * L_out) channel-major.  The two differ in the prefix of their option
+    names and in layer 0.  Parameters conv.i, bn.i, ln.i (both norm holders are always registered,
+    as the reference does), then ln0 / bn0."""
 
     seq_model = False
+    _prefix = None              # option names: <prefix>_N_filt, ...
+    _cgs_suffixes = ("hcgs", "quant", "quant_inp", "prune")
+
+    def _opt(self, key):
+        return getattr(self, "%s_%s" % (self._prefix, key))
 
     def __init__(self, options, inp_dim):
         super().__init__()
-        o = options
+        o, p = options, self._prefix
         self.input_dim = inp_dim
-        self.cnn_N_filt = _lst(o, "cnn_N_filt", int)
-        self.cnn_len_filt = _lst(o, "cnn_len_filt", int)
-        self.cnn_max_pool_len = _lst(o, "cnn_max_pool_len", int)
-        self.cnn_act = _lst(o, "cnn_act")
-        self.cnn_drop = _lst(o, "cnn_drop", float)
-        self.cnn_use_laynorm = _lst(o, "cnn_use_laynorm", strtobool)
-        self.cnn_use_batchnorm = _lst(o, "cnn_use_batchnorm", strtobool)
-        self.cnn_use_laynorm_inp = strtobool(o["cnn_use_laynorm_inp"])
-        self.cnn_use_batchnorm_inp = strtobool(o["cnn_use_batchnorm_inp"])
+        for key, f in (("N_filt", int), ("len_filt", int), ("max_pool_len", int), ("act", str),
+                       ("drop", float), ("use_laynorm", strtobool), ("use_batchnorm", strtobool)):
+            setattr(self, "%s_%s" % (p, key), _lst(o, "%s_%s" % (p, key), f))
+        for key in ("use_laynorm_inp", "use_batchnorm_inp"):
+            setattr(self, "%s_%s" % (p, key), strtobool(o["%s_%s" % (p, key)]))
         self.to_do = o.get("to_do", "train")
-        # core.run_nn / utils read these on every architecture; the reference CNN has no CGS hooks
+        # core.run_nn / utils read these on every architecture; the reference class has no CGS hooks
         self.prune = False
         self.guided_hcgs = False
         self.apply_guided_hcgs = False
         self.if_pattern = False
         self.skip_regularization = strtobool(o.get("skip_regularization", "False"))
-        # the reference CNN has no masks, quantisation or pruning: such keys are refused, not ignored
-        self._cgs_keys = [k for k in ("cnn_hcgs", "cnn_quant", "cnn_quant_inp", "cnn_prune",
-                                      "guided_hcgs", "apply_guided_hcgs", "if_pattern")
+        # the reference class has no masks, quantisation or pruning: such keys are refused, not ignored
+        self._cgs_keys = [k for k in tuple("%s_%s" % (p, s) for s in self._cgs_suffixes) +
+                          ("guided_hcgs", "apply_guided_hcgs", "if_pattern")
                           if strtobool(o.get(k, "False"))]
-        self.N_cnn_lay = len(self.cnn_N_filt)
+        self._read_options(o)
+        N_filt, len_filt, pool = self._opt("N_filt"), self._opt("len_filt"), self._opt("max_pool_len")
+        setattr(self, "N_%s_lay" % p, len(N_filt))
         self.conv, self.bn, self.ln = nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
-        if self.cnn_use_laynorm_inp:
+        if self._opt("use_laynorm_inp"):
             self.ln0 = LayerNorm(inp_dim)
-        if self.cnn_use_batchnorm_inp:
+        if self._opt("use_batchnorm_inp"):
             self.bn0 = nn.BatchNorm1d(inp_dim, momentum=0.05)
         cur, cin = inp_dim, 1
         self.L_in, self.L_out = [], []
-        for i, n in enumerate(self.cnn_N_filt):
-            lout = int((cur - self.cnn_len_filt[i] + 1) / self.cnn_max_pool_len[i])
+        for i, n in enumerate(N_filt):
+            lout = int((cur - len_filt[i] + 1) / pool[i])
             self.ln.append(LayerNorm([n, lout]))
-            # neural_networks.py:1988-1990: nn.BatchNorm1d(N_filt, <L_out>, momentum=0.05) puts
-            # L_out into the second positional parameter, eps: reproduced (eps = L_out)
+            # neural_networks.py:1988-1990 (:2096-2098): nn.BatchNorm1d(N_filt, <L_out>,
+            # momentum=0.05) puts L_out into the second positional parameter, eps: reproduced
             self.bn.append(nn.BatchNorm1d(n, eps=lout, momentum=0.05))
-            self.conv.append(nn.Conv1d(cin, n, self.cnn_len_filt[i]))   # the only RNG draws
+            self.conv.append(self._make_conv(i, cin, n, len_filt[i], o))
             self.L_in.append(cur)
             self.L_out.append(lout)
             cur, cin = lout, n
-        self.out_dim = cur * self.cnn_N_filt[-1]
+        self.out_dim = cur * N_filt[-1]
+
+    def _read_options(self, o):
+        """Options of the subclass's own, read before the layers are built."""
+
+    def _make_conv(self, i, cin, n, length, o):
+        return nn.Conv1d(cin, n, length)            # the only RNG draws
+
+    def _conv_len(self, i):
+        """Taps of layer i's convolution."""
+        return self._opt("len_filt")[i]
 
     def prune_parameters(self):
-        raise NotImplementedError("the reference CNN has no prune hook")
+        raise NotImplementedError("the reference %s has no prune hook" % type(self).__name__)
 
     def forward(self, x):
         """(B, F) -> (B, out_dim) on the pkc kernels, trainable under autograd (pkc.plugin)."""
         return arch_forward(self, x)
 
     def check_supported(self):
+        name, p = type(self).__name__, self._prefix
         if self._cgs_keys:
-            raise NotImplementedError("CNN: %s (the reference CNN has no weight masks, "
-                                      "quantisation or pruning)" % ", ".join(self._cgs_keys))
-        for i in range(self.N_cnn_lay):
-            if self.cnn_use_laynorm[i] and self.cnn_use_batchnorm[i]:
+            raise NotImplementedError("%s: %s (the reference %s has no weight masks, "
+                                      "quantisation or pruning)" % (name, ", ".join(self._cgs_keys), name))
+        for i in range(len(self._opt("N_filt"))):
+            if self._opt("use_laynorm")[i] and self._opt("use_batchnorm")[i]:
                 raise NotImplementedError(
-                    "CNN layer %d has cnn_use_laynorm and cnn_use_batchnorm both set: the "
-                    "reference then applies the convolution twice (neural_networks.py:2019-2025)"
-                    % i)
-            if self.cnn_act[i] == "softmax":
-                raise NotImplementedError("CNN layer %d: softmax on a convolution layer" % i)
+                    "%s layer %d has %s_use_laynorm and %s_use_batchnorm both set: the "
+                    "reference then applies the convolution twice (neural_networks.py:2019-2025, "
+                    ":2129-2135)" % (name, i, p, p))
+            if self._opt("act")[i] == "softmax":
+                raise NotImplementedError("%s layer %d: softmax on a convolution layer" % (name, i))
             if self.L_out[i] < 1:
-                raise ValueError("CNN layer %d has no output (L_out = %d)" % (i, self.L_out[i]))
+                raise ValueError("%s layer %d has no output (L_out = %d)" % (name, i, self.L_out[i]))
 
     def input_norm_specs(self):
-        return _input_norm_specs(self, self.cnn_use_laynorm_inp, self.cnn_use_batchnorm_inp)
+        return _input_norm_specs(self, self._opt("use_laynorm_inp"), self._opt("use_batchnorm_inp"))
 
     def conv_specs(self):
         """Per-layer description consumed by pkc.engine (ConvNode)."""
         specs = []
-        for i, n in enumerate(self.cnn_N_filt):
-            specs.append(dict(C_in=1 if i == 0 else self.cnn_N_filt[i - 1], C_out=n,
-                              L_in=self.L_in[i], L_out=self.L_out[i], len=self.cnn_len_filt[i],
-                              pool=self.cnn_max_pool_len[i], act=self.cnn_act[i],
-                              drop=self.cnn_drop[i], bn=bool(self.cnn_use_batchnorm[i]),
-                              ln=bool(self.cnn_use_laynorm[i]), W=self.conv[i].weight,
-                              b=self.conv[i].bias, gamma=self.bn[i].weight, beta=self.bn[i].bias,
+        N_filt = self._opt("N_filt")
+        for i, n in enumerate(N_filt):
+            conv = self.conv[i]
+            specs.append(dict(C_in=1 if i == 0 else N_filt[i - 1], C_out=n,
+                              L_in=self.L_in[i], L_out=self.L_out[i], len=self._conv_len(i),
+                              pool=self._opt("max_pool_len")[i], act=self._opt("act")[i],
+                              drop=self._opt("drop")[i], bn=bool(self._opt("use_batchnorm")[i]),
+                              ln=bool(self._opt("use_laynorm")[i]), W=getattr(conv, "weight", None),
+                              b=getattr(conv, "bias", None), gamma=self.bn[i].weight,
+                              beta=self.bn[i].bias,
                               rm=self.bn[i].running_mean, rv=self.bn[i].running_var,
                               nbt=self.bn[i].num_batches_tracked, bn_eps=float(self.bn[i].eps),
                               bn_momentum=float(self.bn[i].momentum),
                               ln_gamma=self.ln[i].gamma, ln_beta=self.ln[i].beta,
                               ln_eps=float(self.ln[i].eps)))
+        return specs
+
+
+class CNN(_ConvArch):
+    """neural_networks.py:1934-2033 (options per proto/CNN.proto).  Per layer only the Conv1d
+    draws from the RNG."""
+
+    _prefix = "cnn"
+
+
+class SincConv(nn.Module):
+    """Parameter holder of the reference's SincConv (neural_networks.py:2146-2283): N band-pass
+    filters described by low_hz_ and band_hz_ (N, 1), initialised mel-spaced in units of the
+    sample rate (:2210-2222, no RNG draw).  window_ (K) and n_ (1, K) are plain attributes, not in
+    the state dict; the filters themselves are generated on the GPU (pkc_sinc_filters_fwd)."""
+
+    def __init__(self, out_channels, kernel_size, sample_rate=16000, min_low_hz=50, min_band_hz=50):
+        super().__init__()
+        self.out_channels = out_channels
+        # :2193-2194: an even length is made odd
+        self.kernel_size = kernel_size + 1 if kernel_size % 2 == 0 else kernel_size
+        self.sample_rate, self.min_low_hz, self.min_band_hz = sample_rate, min_low_hz, min_band_hz
+        to_mel = lambda hz: 2595 * np.log10(1 + hz / 700)           # noqa: E731
+        to_hz = lambda mel: 700 * (10 ** (mel / 2595) - 1)          # noqa: E731
+        high_hz = sample_rate / 2 - (min_low_hz + min_band_hz)
+        hz = to_hz(np.linspace(to_mel(30), to_mel(high_hz), out_channels + 1)) / sample_rate
+        self.low_hz_ = nn.Parameter(torch.tensor(hz[:-1], dtype=torch.float32).view(-1, 1))
+        self.band_hz_ = nn.Parameter(torch.tensor(np.diff(hz), dtype=torch.float32).view(-1, 1))
+        K = self.kernel_size
+        # :2226-2232 in torch's fp32, so the rounding is the reference's (the window is the
+        # reference's own: linspace(0, K, K), not a symmetric Hamming window)
+        self.window_ = 0.54 - 0.46 * torch.cos(2 * math.pi * torch.linspace(0, K, steps=K) / K)
+        n = (K - 1) / 2
+        self.n_ = torch.arange(-n, n + 1).view(1, -1) / sample_rate
+
+
+class SincNet(_ConvArch):
+    """neural_networks.py:2036-2143 (options per proto/SincNet.proto): CNN's layers with sinc_*
+    option names, except that layer 0 is a SincConv: its (N, 1, K) weight is a band-pass filter
+    bank regenerated before every forward from conv.0.low_hz_ / conv.0.band_hz_, without bias.
+    No RNG draw in layer 0."""
+
+    _prefix = "sinc"
+
+    def _read_options(self, o):
+        self.sinc_sample_rate = int(o["sinc_sample_rate"])
+        self.sinc_min_low_hz = int(o["sinc_min_low_hz"])
+        self.sinc_min_band_hz = int(o["sinc_min_band_hz"])
+
+    def _make_conv(self, i, cin, n, length, o):
+        if i > 0:
+            return nn.Conv1d(cin, n, length)
+        return SincConv(n, length, sample_rate=self.sinc_sample_rate,
+                        min_low_hz=self.sinc_min_low_hz, min_band_hz=self.sinc_min_band_hz)
+
+    def _conv_len(self, i):
+        return self.conv[0].kernel_size if i == 0 else self.sinc_len_filt[i]
+
+    def check_supported(self):
+        super().check_supported()
+        # neural_networks.py:2094 sizes ln[0] / bn[0] with sinc_len_filt[0] as configured while the
+        # convolution runs with the length :2193-2194 made odd
+        K, pool = self.conv[0].kernel_size, self.sinc_max_pool_len[0]
+        conv_out = int((self.input_dim - K + 1) / pool)
+        if conv_out != self.L_out[0]:
+            raise ValueError(
+                "SincNet: sinc_len_filt[0] = %d is even, so SincConv convolves with %d taps "
+                "(neural_networks.py:2193-2194) and layer 0 yields %d positions, but its "
+                "LayerNorm / BatchNorm are sized for %d (neural_networks.py:2094): the "
+                "reference's forward fails on this shape" % (self.sinc_len_filt[0], K, conv_out,
+                                                             self.L_out[0]))
+
+    def conv_specs(self):
+        specs = super().conv_specs()
+        c = self.conv[0]
+        specs[0]["sinc"] = dict(low=c.low_hz_, band=c.band_hz_, n_=c.n_, window=c.window_,
+                                sr=float(c.sample_rate), min_low_hz=float(c.min_low_hz),
+                                min_band_hz=float(c.min_band_hz))
         return specs
 
 
