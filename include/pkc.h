@@ -506,11 +506,15 @@ int pkc_rnn_persist_geometry(int* nwaves, int* nslots_fwd, int* nslots_bwd, int*
 /* Which time-loop form pkc_rnn_fwd (bwd = 0) / pkc_rnn_bwd (bwd = 1) takes for these arguments:
  * 1 the persistent liGRU loops (persist_* plans above); 2 the persistent grid-synchronised loops —
  * qh_exact LSTM (uni-directional, B <= 16; forward H in {512, 768, 1024}, BPTT H = 512), dense LSTM
- * in bf16 step mode (B2 <= 32, H in {512, 768, 1024}) and liGRU in exact-fp32 step mode
- * (B2 <= 16, H <= 768): the layer's units dealt to H / 16 (liGRU forward: H / 8) workgroups that
- * hand h_t / dgates_t to each other every step; work's floats [4 B2 H, 4 B2 H + 4) hold their step
- * counter and timeout word; 0 one launch per time step.  Environment: PKC_RNN_LSTM_PERSIST=0 and
- * PKC_RNN_LIGRU_GRID=0 disable form 2 for LSTM / liGRU. */
+ * in bf16 or exact-fp32 step mode (B2 <= 32, H in {512, 768, 1024}; fp32: no quantised h, the
+ * grid of H / 16 x ceil(B2 / 16) (BPTT: ceil(B2 / 8)) workgroups within the device's compute
+ * units) and liGRU in exact-fp32 step mode (B2 <= 16, H <= 768): the layer's units dealt to H / 16
+ * (liGRU forward: H / 8) workgroups that hand h_t / dgates_t to each other every step; work's
+ * 288 floats [4 B2 H, 4 B2 H + 288) hold the launch's counter block (a timeout word at
+ * 4 B2 H + 1 and eight step-counter shards on 128-byte lines of their own), which lies inside the
+ * 8 B2 H floats of work, so form 2 needs 4 B2 H >= 288; 0 one launch per time step.
+ * Environment: PKC_RNN_LSTM_PERSIST=0 and PKC_RNN_LIGRU_GRID=0 disable form 2 for LSTM / liGRU,
+ * PKC_RNN_LSTM_F32=0 for the exact-fp32 LSTM alone. */
 int pkc_rnn_persist_form(const pkc_rnn_args* a, int bwd);
 int pkc_rnn_fwd(const pkc_rnn_args* a, void* stream);
 int pkc_rnn_bwd(const pkc_rnn_args* a, float* dpre, void* stream);

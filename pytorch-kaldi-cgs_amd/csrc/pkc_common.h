@@ -4,7 +4,10 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
+
+#include <atomic>
 
 #include "../../include/pkc.h"
 
@@ -41,6 +44,38 @@ void set_error(const char* fmt, ...);
   } while (0)
 
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// The PKC_* environment switches (INTEGRATION.md lists every one).  Read policy: a tuning value is
+// read once per process — its reader keeps it in a function-local `static const`; the five path
+// switches the tests flip within one process (PKC_RNN_LSTM_PERSIST, PKC_RNN_LSTM_F32,
+// PKC_RNN_LIGRU_GRID, PKC_RNN_LSTM_CO, PKC_RNN_LSTM_PERSIST_X3) are read on every call.
+static inline const char* env_str(const char* name) {   // nullptr: unset or empty
+  const char* v = getenv(name);
+  return v && v[0] ? v : nullptr;
+}
+static inline int env_int(const char* name, int dflt) {
+  const char* v = env_str(name);
+  return v ? atoi(v) : dflt;
+}
+// unset or empty: dflt; otherwise off exactly when the value starts with '0'
+static inline bool env_flag(const char* name, bool dflt) {
+  const char* v = env_str(name);
+  return v ? v[0] != '0' : dflt;
+}
+
+// Compute units of the current device (256 when there is none), asked once per device: a
+// grid-synchronised loop needs every workgroup resident at once, and its workgroups are sized for
+// one per CU.
+static inline int device_cus() {
+  static std::atomic<int> cus[64];              // 0: not asked yet
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if ((n = cus[dev].load(std::memory_order_relaxed)) > 0) return n;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+    n = 256;
+  cus[dev].store(n, std::memory_order_relaxed);
+  return n;
+}
 
 // ------------------------------------------------------------------ device helpers
 __device__ __forceinline__ float warp_sum(float v) {

@@ -409,7 +409,7 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 
 // Column group of a workgroup.  Workgroup w runs on XCD w % 8 (round-robin dispatch, observed;
 // speed only — any placement computes the same columns).
-//   XM = 1 (PKC_DENSE_XCD=1, round 1: 0.1976 -> 0.1957 ms per C2 step against launch order): each
+//   XM = 1 (round 1:0.1976 -> 0.1957 ms per C2 step against launch order): each
 //          XCD takes a contiguous run of groups, so the two 64-byte halves of a slab's 128-byte line
 //          are read through one L2 instead of two;
 //   XM = 2 (default since round 3): each XCD takes the 64-column tiles j == XCD (mod 8) — the
@@ -929,23 +929,16 @@ static inline bool al16(const void* p) { return (uintptr_t)p % 16 == 0; }
 // workgroups (B = 4096: 4.74M -> 4.96M frames/s; at B = 1024, 256 workgroups instead of 1024 ran
 // 2.06M -> 2.00M, the small-grid loss the latency-bound BatchNorm kernels show everywhere)
 constexpr int64_t V4_MIN_WG = 1024;
-// the 16-byte large-M forms (PKC_DENSE_V4=0: scalar forms, A/B)
-static bool dense_v4_enabled() {
-  static const int on = [] {
-    const char* v = getenv("PKC_DENSE_V4");
-    return v ? atoi(v) : 1;
-  }();
-  return on != 0;
-}
+// the 16-byte large-M forms (the scalar forms otherwise)
 static bool v4_fwd(const pkc_dense_fwd_args* a) {
-  return dense_v4_enabled() && a->N % 4 == 0 && (a->nslab == 1 || a->slab_stride % 4 == 0) &&
+  return a->N % 4 == 0 && (a->nslab == 1 || a->slab_stride % 4 == 0) &&
          al16(a->zslab) && al16(a->xhat) && al16(a->out) && al16(a->bias) && al16(a->gamma) &&
          al16(a->beta) && al16(a->running_mean) && al16(a->running_var) &&
          (uintptr_t)a->keep_in % 4 == 0 && (uintptr_t)a->keep_out % 4 == 0 &&
          (uintptr_t)a->out_bf16 % 8 == 0;
 }
 static bool v4_bwd(const pkc_dense_bwd_args* a) {
-  return dense_v4_enabled() && a->N % 4 == 0 && (a->nslab == 1 || a->slab_stride % 4 == 0) &&
+  return a->N % 4 == 0 && (a->nslab == 1 || a->slab_stride % 4 == 0) &&
          al16(a->gslab) && al16(a->xhat) && al16(a->dz) && al16(a->gamma) && al16(a->beta) &&
          al16(a->save_invstd) && (uintptr_t)a->keep % 4 == 0 && (uintptr_t)a->dz_bf16 % 8 == 0;
 }
@@ -958,14 +951,6 @@ static bool v4_bwd(const pkc_dense_bwd_args* a) {
 static bool small_ok(int M, int N, int nslab, const void* p0, const void* p1, int64_t stride) {
   return M <= 128 && N % 4 == 0 && nslab <= 8 && ((uintptr_t)p0 % 16 == 0) &&
          ((uintptr_t)p1 % 16 == 0) && (nslab == 1 || stride % 4 == 0);
-}
-
-static int dense_xcd() {                        // PKC_DENSE_XCD=1: the round-1 mapping (A/B)
-  static const int m = [] {
-    const char* v = getenv("PKC_DENSE_XCD");
-    return v ? atoi(v) : 2;
-  }();
-  return m;
 }
 
 #define PKC_SMALL_LAUNCH_X(KERN, G, XM, args, M, nslab, stream)                                  \
@@ -985,10 +970,11 @@ static int dense_xcd() {                        // PKC_DENSE_XCD=1: the round-1 
       else hipLaunchKernelGGL((KERN<8, 2, G, XM>), grid_, dim3(FT), 0, stream, args);          \
     }                                                                                          \
   } while (0)
-// the producer-aligned mapping needs whole 64-column tiles, 8 of them per XCD round
+// the producer-aligned mapping (XM = 2) needs whole 64-column tiles, 8 of them per XCD round; the
+// round-1 mapping (XM = 1) otherwise
 #define PKC_SMALL_LAUNCH_G(KERN, G, args, M, nslab, stream)                                     \
   do {                                                                                         \
-    if (dense_xcd() == 2 && (args).N % 512 == 0)                                               \
+    if ((args).N % 512 == 0)                                                                   \
       PKC_SMALL_LAUNCH_X(KERN, G, 2, args, M, nslab, stream);                                  \
     else                                                                                       \
       PKC_SMALL_LAUNCH_X(KERN, G, 1, args, M, nslab, stream);                                  \

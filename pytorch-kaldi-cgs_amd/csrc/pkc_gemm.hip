@@ -604,17 +604,17 @@ __global__ __launch_bounds__(NT) void gemm_kernel(int M, int N, int K, const voi
                                              B, ldb, C, ldc, kchunk, slab_stride);
 }
 
-// XCD-aware tile order for the standalone 128x128 launches of at most 256 workgroups (PKC_GEMM_XCD,
-// default on; B = 4096 step 3.94-3.96 M -> 4.05-4.06 M frames/s, same run): workgroup
+// XCD-aware tile order for the standalone 128x128 launches of at most 256 workgroups (against
+// launch order: B = 4096 step 3.94-3.96 M -> 4.05-4.06 M frames/s, same run): workgroup
 // w runs on XCD w % 8 (round-robin dispatch), so the linear id is remapped (bijectively, for any
 // grid size) to give each XCD a contiguous run of tiles in (N-tile fastest, M-tile, split) order:
 // the N-tiles of one A row-block share an XCD and its L2, and an XCD reads 1/8 of A instead of
 // all of it.  Speed only: any placement computes the same tiles.
-__device__ __forceinline__ void xcd_tile(int remap, int& bx, int& by, int& bz) {
+__device__ __forceinline__ void xcd_tile(int& bx, int& by, int& bz) {
   const int nx = gridDim.x, ny = gridDim.y;
   const int nwg = nx * ny * gridDim.z;
   int id = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
-  if (remap && nwg >= 16 && nwg <= 256) {     // one workgroup per CU at most (several tiles per
+  if (nwg >= 16 && nwg <= 256) {              // one workgroup per CU at most (several tiles per
                                               // CU measured slower: 8192^3 750 -> 685 TF/s)
     const int xcd = id % 8, q = nwg / 8, r = nwg % 8;
     id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + id / 8;
@@ -631,11 +631,11 @@ __global__ __launch_bounds__(big::NT) void gemm_glds_kernel(int M, int N, int K,
                                                            const void* __restrict__ B, int64_t ldb,
                                                            float* __restrict__ C, int64_t ldc,
                                                            int kchunk, int64_t slab_stride,
-                                                           int remap, const float* __restrict__ bias,
+                                                           const float* __restrict__ bias,
                                                            float* __restrict__ part) {
   __shared__ __attribute__((aligned(16))) char lds[big::gl_lds_bytes<NB>()];
   int bx, by, bz;
-  xcd_tile(remap, bx, by, bz);
+  xcd_tile(bx, by, bz);
   big::body_glds<NB, AKC, BKC, STATS>(lds, bx, by, bz, M, N, K, A, lda, B, ldb, C, ldc, kchunk,
                                       slab_stride, bias, part);
 }
@@ -646,11 +646,11 @@ __global__ __launch_bounds__(big::NT) void gemm_big_kernel(int M, int N, int K,
                                                           const void* __restrict__ B, int64_t ldb,
                                                           float* __restrict__ C, int64_t ldc,
                                                           int kchunk, int64_t slab_stride,
-                                                          int remap, const float* __restrict__ bias,
+                                                          const float* __restrict__ bias,
                                                           float* __restrict__ part) {
   __shared__ __attribute__((aligned(16))) char lds[big::lds_bytes<PREC>()];
   int bx, by, bz;
-  xcd_tile(remap, bx, by, bz);
+  xcd_tile(bx, by, bz);
   big::body<PREC, BIN, AKC, BKC, STATS>(lds, bx, by, bz, M, N, K, A, lda, B, ldb, C, ldc, kchunk,
                                         slab_stride, bias, part);
 }
@@ -799,14 +799,15 @@ __device__ __forceinline__ void grouped_body(const GroupArgs& g) {
 #undef PKC_GB
 }
 
-template <int PREC, bool BIN, bool BIG, bool SP = false, bool SUM = false, int GD = 4,
-          bool VO = false>
+template <int PREC, bool BIN, bool BIG, bool SP = false, bool SUM = false>
 __global__ __launch_bounds__(NT) void gemm_grouped_kernel(GroupArgs g) {
-  grouped_body<PREC, BIN, BIG, SP, SUM, GD, VO>(g);
+  grouped_body<PREC, BIN, BIG, SP, SUM, 4, false>(g);
 }
 
-// The vec-only instance held to 4 waves per SIMD (128 registers): at 113 VGPRs + 16 AGPRs the
-// bf16 form sits one register above that step (PKC_GROUPED_VO=2)
+// Launches whose matmuls are all 16-byte: the vec-only instance held to 4 waves per SIMD (128
+// registers): at 113 VGPRs + 16 AGPRs the bf16 form sits one register above that step.  Same box,
+// two rounds (profiles/r03_grouped_vo_ab.txt): C2 bf16 847-851k / 852-854k / 856-859k frames/s for
+// the general instance / the vec-only instance / this one, the fp32 entry 622k -> 634k
 template <int PREC, bool BIN>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void gemm_grouped_vo4_kernel(GroupArgs g) {
@@ -815,80 +816,19 @@ void gemm_grouped_vo4_kernel(GroupArgs g) {
 
 // k-tiles in flight per workgroup for bf16-stored operands: a stage is one 16-byte register per
 // operand, so depth 8 costs 32 VGPRs more and puts a B = 128 split's whole k-range in flight at
-// once.  Standalone launches (PKC_GEMM_DEPTH, default 8): C2 706k -> 720k, B = 1024 1.97M ->
-// 2.06M frames/s; grouped launches (PKC_GEMM_DEPTH_G, default 4): 8 measured 664-669k, the
-// extra VGPRs cost their optimizer / dW work items residency (same runs)
-// Launches whose matmuls are all 16-byte: PKC_GROUPED_VO=2 (default) the vec-only instance held to
-// 4 waves per SIMD, 1 the vec-only instance, 0 the general instance.  Same box, two rounds
-// (profiles/r03_grouped_vo_ab.txt): C2 bf16 847-851k / 852-854k / 856-859k frames/s for 0 / 1 / 2,
-// the fp32 entry 622k (0) -> 634k (2)
-static int grouped_vo() {
-  static const int m = [] {
-    const char* v = getenv("PKC_GROUPED_VO");
-    return v ? atoi(v) : 2;
-  }();
-  return m;
-}
-
-static int bin_depth(bool grouped = false) {
-  static const int d[2] = {[] {
-    const char* v = getenv("PKC_GEMM_DEPTH");
-    return v && atoi(v) == 4 ? 4 : 8;
-  }(), [] {
-    const char* v = getenv("PKC_GEMM_DEPTH_G");
-    return v && atoi(v) == 8 ? 8 : 4;
-  }()};
-  return d[grouped ? 1 : 0];
-}
-
+// once.  Standalone launches take 8: C2 706k -> 720k, B = 1024 1.97M -> 2.06M frames/s; grouped
+// launches keep 4: 8 measured 664-669k, the extra VGPRs cost their optimizer / dW work items
+// residency (same runs)
 template <int PREC, bool AKC, bool BKC, bool VEC, bool BIN>
 static int launch(int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb,
                   float* C, int64_t ldc, int splits, int64_t slab, hipStream_t s) {
   int kchunk = (K + splits - 1) / splits;
   kchunk = ((kchunk + BK - 1) / BK) * BK;
   dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM, splits);
-  if (BIN && bin_depth() == 8)
-    hipLaunchKernelGGL((gemm_kernel<PREC, AKC, BKC, VEC, 8, BIN>), grid, dim3(NT), 0, s, M, N, K, A,
-                       lda, B, ldb, C, ldc, kchunk, slab);
-  else
-    hipLaunchKernelGGL((gemm_kernel<PREC, AKC, BKC, VEC, 4, BIN>), grid, dim3(NT), 0, s, M, N, K, A,
-                       lda, B, ldb, C, ldc, kchunk, slab);
+  hipLaunchKernelGGL((gemm_kernel<PREC, AKC, BKC, VEC, BIN ? 8 : 4, BIN>), grid, dim3(NT), 0, s, M,
+                     N, K, A, lda, B, ldb, C, ldc, kchunk, slab);
   PKC_LAUNCH_CHECK("pkc_gemm");
   return PKC_OK;
-}
-
-static int xcd_remap() {                      // PKC_GEMM_XCD=0: launch order (A/B)
-  static const int on = [] {
-    const char* v = getenv("PKC_GEMM_XCD");
-    return v ? atoi(v) : 1;
-  }();
-  return on;
-}
-
-// PKC_GEMM_COLSTATS64=0: column statistics in the 128x128 body only (A/B)
-static bool colstats64_enabled() {
-  static const int on = [] {
-    const char* v = getenv("PKC_GEMM_COLSTATS64");
-    return v ? atoi(v) : 1;
-  }();
-  return on != 0;
-}
-
-static bool glds_enabled() {                   // PKC_GEMM_GLDS=0: register-staged body (A/B)
-  static const int on = [] {
-    const char* v = getenv("PKC_GEMM_GLDS");
-    return v ? atoi(v) : 1;
-  }();
-  return on != 0;
-}
-
-static int glds_bufs() {                      // PKC_GLDS_BUFS: LDS-DMA ring depth (3, 4, 5)
-  static const int nb = [] {
-    const char* v = getenv("PKC_GLDS_BUFS");
-    const int n = v ? atoi(v) : 3;
-    return n < 3 ? 3 : n > 5 ? 5 : n;
-  }();
-  return nb;
 }
 
 template <int PREC, bool BIN, bool STATS = false>
@@ -903,27 +843,21 @@ static int launch_big(int akc, int bkc, int M, int N, int K, const void* A, int6
   // 4096x1024x1024 27.8 -> 21.8 us (forward) / 27.7 -> 20.3 (dX); with several tiles per CU its
   // 96 KB of LDS (one workgroup per CU) loses to the register body (4096x1928x1024 31.6 -> 35.3,
   // 8192^3 755 -> 656 TF/s), same run
-  if (BIN && K % 64 == 0 && (int64_t)grid.x * grid.y * grid.z <= 256 && glds_enabled()) {
-#define PKC_L(NB, AK, BK_)                                                                      \
-  hipLaunchKernelGGL((gemm_glds_kernel<NB, AK, BK_, STATS>), grid, dim3(big::NT), 0, s, M, N, K, A, \
-                     lda, B, ldb, C, ldc, kchunk, slab, xcd_remap(), bias, part)
-#define PKC_LN(NB)                                                                              \
-  if (akc && bkc) PKC_L(NB, true, true);                                                        \
-  else if (akc) PKC_L(NB, true, false);                                                         \
-  else if (bkc) PKC_L(NB, false, true);                                                         \
-  else PKC_L(NB, false, false)
-    const int nb = glds_bufs();
-    if (nb == 5) { PKC_LN(5); }
-    else if (nb == 4) { PKC_LN(4); }
-    else { PKC_LN(3); }
-#undef PKC_LN
+  if (BIN && K % 64 == 0 && (int64_t)grid.x * grid.y * grid.z <= 256) {
+#define PKC_L(AK, BK_)                                                                          \
+  hipLaunchKernelGGL((gemm_glds_kernel<3, AK, BK_, STATS>), grid, dim3(big::NT), 0, s, M, N, K, A, \
+                     lda, B, ldb, C, ldc, kchunk, slab, bias, part)
+    if (akc && bkc) PKC_L(true, true);
+    else if (akc) PKC_L(true, false);
+    else if (bkc) PKC_L(false, true);
+    else PKC_L(false, false);
 #undef PKC_L
     PKC_LAUNCH_CHECK("pkc_gemm (128x128 LDS-DMA)");
     return PKC_OK;
   }
 #define PKC_L(AK, BK_)                                                                          \
   hipLaunchKernelGGL((gemm_big_kernel<PREC, BIN, AK, BK_, STATS>), grid, dim3(big::NT), 0, s, M, N, \
-                     K, A, lda, B, ldb, C, ldc, kchunk, slab, xcd_remap(), bias, part)
+                     K, A, lda, B, ldb, C, ldc, kchunk, slab, bias, part)
   if (akc && bkc) PKC_L(true, true);
   else if (akc) PKC_L(true, false);
   else if (bkc) PKC_L(false, true);
@@ -951,23 +885,11 @@ static int dispatch(int akc, int bkc, bool vec, int M, int N, int K, const void*
 // chip; in a grouped launch the other problems fill it).  In a grouped launch it also needs a long
 // contraction: its 64 KB of LDS cuts the residency of every other workgroup of the launch, which
 // the B = 128 step's short dW (K = 128) launches cannot afford (681k -> 627k frames/s when they
-// took it).  PKC_GEMM_BIG=0 disables it (A/B runs).
+// took it).  PKC_GEMM_BIG=0 disables it (A/B runs, scripts/gemm_bench.py).
 constexpr int BIG_MIN_TILES = 160, BIG_MIN_TILES_GROUPED = 32, BIG_MIN_K_GROUPED = 1024;
 static bool big_enabled() {
-  static const int on = [] {
-    const char* v = getenv("PKC_GEMM_BIG");
-    return v ? atoi(v) : 1;
-  }();
-  return on != 0;
-}
-// compensated-bf16 problems of grouped launches on the 128x128 body (PKC_X3_GROUPED_BIG=0: the
-// 64x64 body, whose grouped instances keep several workgroups per CU)
-static bool x3_grouped_big() {
-  static const int on = [] {
-    const char* v = getenv("PKC_X3_GROUPED_BIG");
-    return v ? atoi(v) : 1;
-  }();
-  return on != 0;
+  static const bool on = env_flag("PKC_GEMM_BIG", true);
+  return on;
 }
 
 }  // namespace pkc
@@ -1051,7 +973,7 @@ extern "C" int pkc_gemm_grouped_tile(int prec, int a_kcontig, int b_kcontig, int
                                      const void* A, int64_t lda, const void* B, int64_t ldb) {
   using namespace pkc;
   if (M <= 0 || N <= 0 || K <= 0 || lda <= 0 || ldb <= 0) return 64;
-  return big_enabled() && (prec != PKC_PREC_BF16X3 || x3_grouped_big()) &&
+  return big_enabled() &&
                  big::eligible(prec, a_kcontig, b_kcontig, M, N, K, A, lda, B, ldb,
                                BIG_MIN_TILES_GROUPED, BIG_MIN_K_GROUPED) ? 128 : 64;
 }
@@ -1072,7 +994,7 @@ extern "C" int pkc_gemm_colstats_ok(int prec, int a_kcontig, int b_kcontig, int 
   const bool vec = ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && lda % e == 0 &&
                    ldb % e == 0 && (a_kcontig ? K % e == 0 : M % e == 0) &&
                    (b_kcontig ? K % e == 0 : N % e == 0);
-  return vec && colstats64_enabled() ? 64 : 0;
+  return vec ? 64 : 0;
 }
 
 extern "C" int pkc_gemm_colstats(int prec, int a_kcontig, int b_kcontig, int M, int N, int K,
@@ -1222,7 +1144,7 @@ extern "C" int pkc_gemm_grouped(int prec, const pkc_gemm_problem* probs, int n, 
     const bool vec = ((uintptr_t)q.A % 16 == 0) && ((uintptr_t)q.B % 16 == 0) && q.lda % e == 0 &&
                      q.ldb % e == 0 && (q.a_kcontig ? q.K % e == 0 : q.M % e == 0) &&
                      (q.b_kcontig ? q.K % e == 0 : q.N % e == 0);
-    const bool bigp = !any_sparse && big_enabled() && (prec != PKC_PREC_BF16X3 || x3_grouped_big()) &&
+    const bool bigp = !any_sparse && big_enabled() &&
                       big::eligible(prec, q.a_kcontig, q.b_kcontig, q.M, q.N, q.K,
                                                      q.A, q.lda, q.B, q.ldb, BIG_MIN_TILES_GROUPED,
                                                      BIG_MIN_K_GROUPED);
@@ -1273,14 +1195,8 @@ extern "C" int pkc_gemm_grouped(int prec, const pkc_gemm_problem* probs, int n, 
                          S(stream), g);                                                         \
     else if (any_big)                                                                           \
       hipLaunchKernelGGL((gemm_grouped_kernel<P, BIN, true>), dim3(wg), dim3(NT), 0, S(stream), g);  \
-    else if (BIN && bin_depth(true) == 8)                                                       \
-      hipLaunchKernelGGL((gemm_grouped_kernel<P, BIN, false, false, false, 8>), dim3(wg), dim3(NT), \
-                         0, S(stream), g);                                                      \
-    else if (all_vec && grouped_vo() == 2)                                                      \
+    else if (all_vec)                                                                           \
       hipLaunchKernelGGL((gemm_grouped_vo4_kernel<P, BIN>), dim3(wg), dim3(NT), 0, S(stream), g); \
-    else if (all_vec && grouped_vo() == 1)                                                      \
-      hipLaunchKernelGGL((gemm_grouped_kernel<P, BIN, false, false, false, 4, true>), dim3(wg),  \
-                         dim3(NT), 0, S(stream), g);                                            \
     else                                                                                        \
       hipLaunchKernelGGL((gemm_grouped_kernel<P, BIN, false>), dim3(wg), dim3(NT), 0, S(stream), g); \
   } while (0)
@@ -1304,7 +1220,7 @@ extern "C" int pkc_gemm_grouped(int prec, const pkc_gemm_problem* probs, int n, 
     else if (any_sum)
       hipLaunchKernelGGL((gemm_grouped_kernel<P, false, false, false, true>), dim3(wg), dim3(NT), 0,
                          S(stream), g);
-    else if (all_vec && grouped_vo() == 2)
+    else if (all_vec)
       hipLaunchKernelGGL((gemm_grouped_vo4_kernel<P, false>), dim3(wg), dim3(NT), 0, S(stream), g);
     else
       hipLaunchKernelGGL((gemm_grouped_kernel<P, false, false>), dim3(wg), dim3(NT), 0, S(stream), g);

@@ -582,7 +582,8 @@ __device__ __forceinline__ void body(char* __restrict__ lds, int bx, int by, int
 // (swz for row images, xr for the [k][row] images) go on the per-lane SOURCE addresses instead.
 // NB buffers in the ring, NB - 1 k-tiles in flight: a lone workgroup per CU keeps only
 // (NB - 1) x 32 KB of operand requests outstanding, so its k-tile rate is that over the load
-// latency under full-chip traffic (PKC_GLDS_BUFS selects NB = 3, 4 or 5; 5 = all 160 KB of LDS).
+// latency under full-chip traffic (the launcher takes NB = 3: 4 and 5, all 160 KB of LDS, did not
+// move the k-tile rate).
 template <int NB>
 constexpr int gl_lds_bytes() { return NB * 2 * TILE_BYTES; }
 

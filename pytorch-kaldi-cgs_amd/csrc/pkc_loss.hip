@@ -387,14 +387,10 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(int nheads, const fl
 
 }  // namespace pkc
 
-// the 16-byte form: whole float4 column chunks, aligned rows (PKC_NLL_VEC=0: scalar form, A/B)
+// the 16-byte form: whole float4 column chunks, aligned rows (the scalar form otherwise)
 static bool nll_vec_ok(const pkc_nll_args* a) {
-  static const int on = [] {
-    const char* v = getenv("PKC_NLL_VEC");
-    return v ? atoi(v) : 1;
-  }();
   auto al = [](const void* p, int b) { return ((uintptr_t)p % b) == 0; };
-  return on && a->N % 4 == 0 && a->N >= 4 && (a->nslab == 1 || a->slab_stride % 4 == 0) &&
+  return a->N % 4 == 0 && a->N >= 4 && (a->nslab == 1 || a->slab_stride % 4 == 0) &&
          al(a->zslab, 16) && al(a->logp, 16) && al(a->dlogits, 16) && al(a->bias, 16) &&
          al(a->log_prior, 16) && al(a->dlogits_bf16, 8);
 }

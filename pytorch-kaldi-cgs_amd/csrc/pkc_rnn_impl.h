@@ -1204,42 +1204,21 @@ struct SCase {};
 
 static int pick_vw(int H) { return H % 4 == 0 ? 4 : (H % 2 == 0 ? 2 : 1); }
 
-// 16-row step tiles up to 2B <= PKC_RNN_ROWS16 rows (default 16; 0: always the 32-row tiles).
-// Clamped to 16: a 16-row tile holds rows [16 y, 16 y + 16) only, so with more rows the grid would
-// have two row tiles — and the quantised-h step takes var (max |h_{t-1}|) from ONE tile's registers.
-static bool rows16(int B2) {
-  static const int lim = [] {
-    const char* v = getenv("PKC_RNN_ROWS16");
-    const int l = v ? atoi(v) : 16;
-    return l < 16 ? l : 16;
-  }();
-  return B2 <= lim;
-}
+// 16-row step tiles up to 2B <= 16 rows.  A 16-row tile holds rows [16 y, 16 y + 16) only, so with
+// more rows the grid would have two row tiles — and the quantised-h step takes var (max |h_{t-1}|)
+// from ONE tile's registers.
+static bool rows16(int B2) { return B2 <= 16; }
 
 // 8-wave step tiles for the dense one-phase cells at S >= 32 (H > 256): half the operand strip
-// per lane and half the MFMA chain per wave.  Same-run A/B (PKC_RNN_WAVES=4 / 8): C4 89.2k / 90.8k,
-// C5 (8-wave BPTT only; its quantised forward keeps 4) 117.6k / 120.3k frames/s — the step is
+// per lane and half the MFMA chain per wave.  Same-run A/B against 4-wave tiles: C4 89.2k / 90.8k,
+// C5 (8-wave BPTT only; its quantised forward kept 4) 117.6k / 120.3k frames/s — the step is
 // bound by h_{t-1} arriving from the other XCDs, not by the per-lane load or MFMA work.
-// PKC_RNN_QH_WAVES (8 / 4): the quantised-h forward step (C5) as 8-wave tiles — half the strip,
-// quantisation passes and MFMA chains per wave, two waves per SIMD to overlap one's
-// quantisation arithmetic with the other's MFMAs
-// (16-wave tiles of the exact form measured 20.05 vs 19.95 us per step.layer: the quantisation
-// arithmetic is per-CU work, more waves only split it)
-static bool qh_eight_waves(int S) {
-  static const int w = [] {
-    const char* v = getenv("PKC_RNN_QH_WAVES");
-    return v ? atoi(v) : 8;
-  }();
-  return w == 8 && S >= 32;
-}
-
-static bool eight_waves(int S) {
-  static const int w = [] {
-    const char* v = getenv("PKC_RNN_WAVES");
-    return v ? atoi(v) : 8;
-  }();
-  return w == 8 && S >= 32;
-}
+// The quantised-h forward step (C5) as 8-wave tiles: half the strip, quantisation passes and MFMA
+// chains per wave, two waves per SIMD to overlap one's quantisation arithmetic with the other's
+// MFMAs (16-wave tiles of the exact form measured 20.05 vs 19.95 us per step.layer: the
+// quantisation arithmetic is per-CU work, more waves only split it)
+template <int S, bool SP>
+constexpr int step_waves = !SP && S >= 32 ? 8 : 4;
 
 #ifdef PKC_RNN_FWD
 template <int G, int CELL, int S, bool SP = false>
@@ -1269,68 +1248,48 @@ static int fwd_impl_s(const pkc_rnn_args* a, hipStream_t s) {
     // 2B <= 16 rows (C3, C5): 16-row tiles, no second MFMA chain or operand strip
     const bool r16 = rows16(B2);
     const dim3 g16(g1.x, rows_16);
+    constexpr int NW = step_waves<S, SP>, WS = S * 4 / NW;   // waves, strip per lane
+    const dim3 nt(64 * NW);
     if constexpr (!SP) {
       if (a->step_bf16) {              // bf16 step products (check(): dense, no qbits / LN)
-        const bool ew = eight_waves(S);
         for (int t = 0; t < a->T; ++t) {
-          if (r16 && ew)
-            hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S / 2, false, false, 8, true, true>),
-                               g16, dim3(2 * RT), 0, s, *a, t, vw);
-          else if (r16)
-            hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, false, 4, true, true>),
-                               g16, dim3(RT), 0, s, *a, t, vw);
-          else if (ew)
-            hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S / 2, false, false, 8, false, true>),
-                               g1, dim3(2 * RT), 0, s, *a, t, vw);
+          if (r16)
+            hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, WS, false, false, NW, true, true>), g16, nt,
+                               0, s, *a, t, vw);
           else
-            hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, false, 4, false, true>),
-                               g1, dim3(RT), 0, s, *a, t, vw);
+            hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, WS, false, false, NW, false, true>), g1, nt,
+                               0, s, *a, t, vw);
         }
         PKC_LAUNCH_CHECK("pkc_rnn_fwd bf16 step");
         return PKC_OK;
       }
     }
     for (int t = 0; t < a->T; ++t) {
-      if (r16) {
-        if constexpr (SP) {
-          if (a->step_bf16)
-            hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true, 4, true, true>), g16,
-                               dim3(RT), 0, s, *a, t, vw);
-          else
-            hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true, 4, true>), g16, dim3(RT), 0, s,
-                               *a, t, vw);
-        } else if (a->qbits > 0 && qh_eight_waves(S)) {
-          bool done = false;
-          if constexpr (CELL == PKC_CELL_LSTM && (S / 2) % 8 == 0)
-            if ((done = a->qh_exact != 0))
-              hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S / 2, true, false, 8, true, false, true>),
-                                 g16, dim3(2 * RT), 0, s, *a, t, vw);
-          if (!done)
-            hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S / 2, true, false, 8, true>), g16,
-                               dim3(2 * RT), 0, s, *a, t, vw);
-        } else if (a->qbits > 0) {
-          bool done = false;
-          if constexpr (CELL == PKC_CELL_LSTM && S % 8 == 0)
-            if ((done = a->qh_exact != 0))
-              hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, true, false, 4, true, false, true>), g16,
-                                 dim3(RT), 0, s, *a, t, vw);
-          if (!done)
-            hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, true, false, 4, true>), g16, dim3(RT), 0,
-                               s, *a, t, vw);
-        }
-        else if (eight_waves(S))
-          hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S / 2, false, false, 8, true>), g16,
-                             dim3(2 * RT), 0, s, *a, t, vw);
+      if constexpr (SP) {
+        if (r16 && a->step_bf16)
+          hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true, 4, true, true>), g16, nt, 0, s,
+                             *a, t, vw);
+        else if (r16)
+          hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true, 4, true>), g16, nt, 0, s, *a,
+                             t, vw);
+        else if (a->step_bf16)
+          hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true, 4, false, true>), g1, nt, 0, s,
+                             *a, t, vw);
         else
-          hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, false, 4, true>), g16, dim3(RT), 0,
-                             s, *a, t, vw);
-      } else if constexpr (SP) {
-        if (a->step_bf16)
-          hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true, 4, false, true>), g1,
-                             dim3(RT), 0, s, *a, t, vw);
-        else
-          hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true>), g1, dim3(RT), 0, s, *a, t, vw);
-      } else if (a->qbits > 0) {
+          hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true>), g1, nt, 0, s, *a, t, vw);
+      } else if (r16 && a->qbits > 0) {
+        bool done = false;
+        if constexpr (CELL == PKC_CELL_LSTM && WS % 8 == 0)
+          if ((done = a->qh_exact != 0))
+            hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, WS, true, false, NW, true, false, true>), g16,
+                               nt, 0, s, *a, t, vw);
+        if (!done)
+          hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, WS, true, false, NW, true>), g16, nt, 0, s, *a,
+                             t, vw);
+      } else if (r16) {
+        hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, WS, false, false, NW, true>), g16, nt, 0, s, *a,
+                           t, vw);
+      } else if (a->qbits > 0) {       // (more than 16 rows: the quantised-h step keeps 4 waves)
         bool done = false;
         if constexpr (CELL == PKC_CELL_LSTM && S % 8 == 0)
           if ((done = a->qh_exact != 0))
@@ -1338,12 +1297,9 @@ static int fwd_impl_s(const pkc_rnn_args* a, hipStream_t s) {
                                dim3(RT), 0, s, *a, t, vw);
         if (!done)
           hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, true>), g1, dim3(RT), 0, s, *a, t, vw);
+      } else {
+        hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, WS, false, false, NW>), g1, nt, 0, s, *a, t, vw);
       }
-      else if (eight_waves(S))
-        hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S / 2, false, false, 8>), g1, dim3(2 * RT), 0, s,
-                           *a, t, vw);
-      else
-        hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false>), g1, dim3(RT), 0, s, *a, t, vw);
       if (a->ln_gamma) hipLaunchKernelGGL(rnn_ln_fwd, dim3((B2 + 3) / 4), dim3(256), 0, s, *a, t);
     }
   }
@@ -1402,33 +1358,25 @@ static int bwd_impl_s(const pkc_rnn_args* a, float* dpre, hipStream_t s) {
       mm2(tt);
     }
   } else {
+    constexpr int NW = step_waves<S, SP>, WS = S * 4 / NW;   // waves, strip per lane
+    const dim3 nt(64 * NW), gg(kt, r16 ? rows_16 : rows, G);
     if constexpr (!SP) {
       if (a->step_bf16) {              // bf16 BPTT products (dgates_h x ut_h)
-        const bool ew = eight_waves(S);
         for (int tt = a->T - 2; tt >= 0; --tt) {
           if constexpr (G == 1) {
             if (r16)
-              hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S, false, 4, true, true>),
-                                 dim3(kt, rows_16, 1), dim3(RT), 0, s, *a, tt + 1,
-                                 0, vw);
+              hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S, false, 4, true, true>), gg, dim3(RT), 0,
+                                 s, *a, tt + 1, 0, vw);
             else
-              hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S, false, 4, false, true>),
-                                 dim3(kt, rows, 1), dim3(RT), 0, s, *a, tt + 1, 0,
-                                 vw);
+              hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S, false, 4, false, true>), gg, dim3(RT), 0,
+                                 s, *a, tt + 1, 0, vw);
           } else {
-            const dim3 gg(kt, r16 ? rows_16 : rows, G);
-            if (r16 && ew)
-              hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S / 2, false, 8, true, true>),
-                                 gg, dim3(2 * RT), 0, s, *a, tt + 1, 0, vw);
-            else if (r16)
-              hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S, false, 4, true, true>),
-                                 gg, dim3(RT), 0, s, *a, tt + 1, 0, vw);
-            else if (ew)
-              hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S / 2, false, 8, false, true>),
-                                 gg, dim3(2 * RT), 0, s, *a, tt + 1, 0, vw);
+            if (r16)
+              hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, WS, false, NW, true, true>), gg, nt, 0, s,
+                                 *a, tt + 1, 0, vw);
             else
-              hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S, false, 4, false, true>),
-                                 gg, dim3(RT), 0, s, *a, tt + 1, 0, vw);
+              hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, WS, false, NW, false, true>), gg, nt, 0, s,
+                                 *a, tt + 1, 0, vw);
             hipLaunchKernelGGL((rnn_bwd_epi<G, CELL, G, true>), dim3(eb), dim3(256), 0, s,
                                *a, tt);
           }
@@ -1442,36 +1390,34 @@ static int bwd_impl_s(const pkc_rnn_args* a, float* dpre, hipStream_t s) {
     for (int tt = a->T - 2; tt >= 0; --tt) {
       if constexpr (G == 1) {
         if (r16)
-          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S, false, 4, true>), dim3(kt, rows_16, 1),
-                             dim3(RT), 0, s, *a, tt + 1, 0, vw);
-        else
-          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S>), dim3(kt, rows, 1), dim3(RT), 0, s, *a,
+          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S, false, 4, true>), gg, dim3(RT), 0, s, *a,
                              tt + 1, 0, vw);
-      } else if (r16) {                               // 16-row tiles (C3, C5)
-        if (!SP && eight_waves(S))
-          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S / 2, false, 8, true>), dim3(kt, rows_16, G), dim3(2 * RT), 0, s, *a, tt + 1, 0, vw);
-        else if (SP && a->step_bf16)
-          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S, SP, 4, true, true>), dim3(kt, rows_16, G),
-                             dim3(RT), 0, s, *a, tt + 1, 0, vw);
         else
-          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S, SP, 4, true>), dim3(kt, rows_16, G),
-                             dim3(RT), 0, s, *a, tt + 1, 0, vw);
-        if (SP && a->step_bf16)
+          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S>), gg, dim3(RT), 0, s, *a, tt + 1, 0, vw);
+      } else {
+        bool bf = false;
+        if constexpr (SP) {                           // block-sparse U with bf16 step products
+          if ((bf = a->step_bf16 != 0)) {
+            if (r16)
+              hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S, SP, 4, true, true>), gg, nt, 0, s, *a,
+                                 tt + 1, 0, vw);
+            else
+              hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S, SP, 4, false, true>), gg, nt, 0, s, *a,
+                                 tt + 1, 0, vw);
+          }
+        }
+        if (!bf) {
+          if (r16)                                    // 16-row tiles (C3, C5)
+            hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, WS, SP, NW, true>), gg, nt, 0, s, *a, tt + 1,
+                               0, vw);
+          else
+            hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, WS, SP, NW>), gg, nt, 0, s, *a, tt + 1, 0,
+                               vw);
+        }
+        if (bf)
           hipLaunchKernelGGL((rnn_bwd_epi<G, CELL, G, true>), dim3(eb), dim3(256), 0, s, *a, tt);
         else
           hipLaunchKernelGGL((rnn_bwd_epi<G, CELL, G>), dim3(eb), dim3(256), 0, s, *a, tt);
-      } else if (!SP && eight_waves(S)) {
-        hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S / 2, false, 8>), dim3(kt, rows, G),
-                           dim3(2 * RT), 0, s, *a, tt + 1, 0, vw);
-        hipLaunchKernelGGL((rnn_bwd_epi<G, CELL, G>), dim3(eb), dim3(256), 0, s, *a, tt);
-      } else if (SP && a->step_bf16) {
-        hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S, SP, 4, false, true>), dim3(kt, rows, G),
-                           dim3(RT), 0, s, *a, tt + 1, 0, vw);
-        hipLaunchKernelGGL((rnn_bwd_epi<G, CELL, G, true>), dim3(eb), dim3(256), 0, s, *a, tt);
-      } else {
-        hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S, SP>), dim3(kt, rows, G), dim3(RT), 0, s, *a,
-                           tt + 1, 0, vw);
-        hipLaunchKernelGGL((rnn_bwd_epi<G, CELL, G>), dim3(eb), dim3(256), 0, s, *a, tt);
       }
       if (ln) hipLaunchKernelGGL((rnn_ln_bwd_gates<G, CELL>), lg, dim3(256), 0, s, *a, tt);
     }
@@ -1507,6 +1453,9 @@ int rnn_lstm_persist_bwd(const pkc_rnn_args* a, hipStream_t s);
 bool rnn_ligru_grid_ok(const pkc_rnn_args* a, bool bwd);
 int rnn_ligru_grid_fwd(const pkc_rnn_args* a, hipStream_t s);
 int rnn_ligru_grid_bwd(const pkc_rnn_args* a, hipStream_t s);
+// the form these arguments take (pkc_rnn_lstm_persist.hip): 0 one launch per step, 1 rnn_persist_*,
+// 2 rnn_lstm_persist_*, 3 rnn_ligru_grid_*
+int rnn_loop_form(const pkc_rnn_args* a, bool bwd);
 
 namespace {
 
@@ -1524,12 +1473,11 @@ static int fwd_impl(const pkc_rnn_args* a, hipStream_t s) {
     hipLaunchKernelGGL(rnn_drop_mask_kernel, dim3(64), dim3(256), 0, s, *a, B2);
     PKC_LAUNCH_CHECK("pkc_rnn_fwd drop mask");
   }
-  if constexpr (CELL == PKC_CELL_LIGRU) {
-    if (rnn_persist_ok(a, false)) return rnn_persist_fwd(a, s);
-    if (rnn_ligru_grid_ok(a, false)) return rnn_ligru_grid_fwd(a, s);
-  }
-  if constexpr (CELL == PKC_CELL_LSTM) {
-    if (rnn_lstm_persist_ok(a, false)) return rnn_lstm_persist_fwd(a, s);
+  switch (rnn_loop_form(a, false)) {
+    case 1: return rnn_persist_fwd(a, s);
+    case 2: return rnn_lstm_persist_fwd(a, s);
+    case 3: return rnn_ligru_grid_fwd(a, s);
+    default: break;                            // one launch per step
   }
   if constexpr (!two_phase(CELL) && G > 1) {
     if (a->kmap_fwd) {
@@ -1545,44 +1493,17 @@ static int fwd_impl(const pkc_rnn_args* a, hipStream_t s) {
 #ifdef PKC_RNN_BWD
 template <int G, int CELL>
 static int bwd_impl(const pkc_rnn_args* a, float* dpre, hipStream_t s) {
-  if constexpr (CELL == PKC_CELL_LIGRU) {
-    if (rnn_persist_ok(a, true)) {
-      const int H = a->H;
-      hipLaunchKernelGGL(rnn_transpose_u, dim3((H + 31) / 32, (H + 31) / 32, G), dim3(256), 0, s, *a);
-      hipLaunchKernelGGL((rnn_bwd_init<G, CELL>), dim3(64), dim3(256), 0, s, *a);
-      PKC_LAUNCH_CHECK("pkc_rnn_bwd init");
-      int st = rnn_persist_bwd(a, s);
-      if (st) return st;
-      hipLaunchKernelGGL(rnn_fold_kernel, dim3(1024), dim3(256), 0, s, *a, dpre);
-      PKC_LAUNCH_CHECK("pkc_rnn_bwd fold");
-      return PKC_OK;
-    }
-  }
-  if constexpr (CELL == PKC_CELL_LIGRU) {
-    if (rnn_ligru_grid_ok(a, true)) {
-      const int H = a->H;
-      hipLaunchKernelGGL(rnn_transpose_u, dim3((H + 31) / 32, (H + 31) / 32, G), dim3(256), 0, s, *a);
-      hipLaunchKernelGGL((rnn_bwd_init<G, CELL>), dim3(64), dim3(256), 0, s, *a);
-      PKC_LAUNCH_CHECK("pkc_rnn_bwd init");
-      int st = rnn_ligru_grid_bwd(a, s);
-      if (st) return st;
-      hipLaunchKernelGGL(rnn_fold_kernel, dim3(1024), dim3(256), 0, s, *a, dpre);
-      PKC_LAUNCH_CHECK("pkc_rnn_bwd fold");
-      return PKC_OK;
-    }
-  }
-  if constexpr (CELL == PKC_CELL_LSTM) {
-    if (rnn_lstm_persist_ok(a, true)) {
-      const int H = a->H;
-      hipLaunchKernelGGL(rnn_transpose_u, dim3((H + 31) / 32, (H + 31) / 32, G), dim3(256), 0, s, *a);
-      hipLaunchKernelGGL((rnn_bwd_init<G, CELL>), dim3(64), dim3(256), 0, s, *a);
-      PKC_LAUNCH_CHECK("pkc_rnn_bwd init");
-      int st = rnn_lstm_persist_bwd(a, s);
-      if (st) return st;
-      hipLaunchKernelGGL(rnn_fold_kernel, dim3(1024), dim3(256), 0, s, *a, dpre);
-      PKC_LAUNCH_CHECK("pkc_rnn_bwd fold");
-      return PKC_OK;
-    }
+  if (const int form = rnn_loop_form(a, true)) {
+    const int H = a->H;
+    hipLaunchKernelGGL(rnn_transpose_u, dim3((H + 31) / 32, (H + 31) / 32, G), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL((rnn_bwd_init<G, CELL>), dim3(64), dim3(256), 0, s, *a);
+    PKC_LAUNCH_CHECK("pkc_rnn_bwd init");
+    const int st = form == 1 ? rnn_persist_bwd(a, s)
+                   : form == 2 ? rnn_lstm_persist_bwd(a, s) : rnn_ligru_grid_bwd(a, s);
+    if (st) return st;
+    hipLaunchKernelGGL(rnn_fold_kernel, dim3(1024), dim3(256), 0, s, *a, dpre);
+    PKC_LAUNCH_CHECK("pkc_rnn_bwd fold");
+    return PKC_OK;
   }
   if constexpr (!two_phase(CELL) && G > 1) {
     if (a->kmap_bwd) {

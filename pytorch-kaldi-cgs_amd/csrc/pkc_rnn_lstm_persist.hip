@@ -22,7 +22,10 @@
 //     timeout word (counter + 1) and ends;
 //   * the step's inputs that do not depend on the recurrence (W x, dL/dy, saved gates) are
 //     requested before the wait, so they arrive during it.
-// Numerics: bit-identical to the per-step kernels (tests/test_gpu_lstm_persist.py):
+// Numerics: bit-identical to the per-step kernels only with PKC_RNN_LSTM_PERSIST_X3=0 (the QX
+// BPTT's fp32 chains) and PKC_RNN_LSTM_CO=0 (the bf16 loops' per-step chunking); with the defaults
+// (compensated-bf16 QX BPTT products, coalesced bf16 chunking) within the bounds of
+// tests/test_gpu_lstm_persist.py.  The bit-identical forms:
 //   forward: the per-step QX kernel's per-wave k-ranges (wave w: [w H / 8, (w + 1) H / 8)), whose
 //     kh / kl x U_h sums are exact integers in any order, the same fmaf(256, hi, lo) x var_s per
 //     wave, the same ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)) across waves, then fwd_epi;
@@ -453,7 +456,7 @@ __global__ __launch_bounds__(BNT) void bwd_loop(pkc_rnn_args a) {
 // k at + 8 i, two 16-row chains, the waves' partials summed ((0 + 1) + (2 + 3)) + ((4 + 5) +
 // (6 + 7)); the handed-off operand is the bf16 copy the per-step kernels read (hs_h, dgates_h),
 // stored as pairs of adjacent units.
-// RS = 2 / 4 (B2 > 16, C4's 32 rows): the rows are split over RS workgroups per unit block
+// RS = 2 (forward) / 4 (BPTT) (B2 > 16, C4's 32 rows): the rows are split over RS workgroups per unit block
 // (blockIdx.y = row block of 32 / RS rows, RS H / 16 workgroups): each reads and multiplies only
 // its rows of the handed-off operand (a 16-row MFMA tile, rows past the block reading zeros
 // without a memory access) — 1 / RS of the per-workgroup payload, which bounds the BPTT step
@@ -690,9 +693,9 @@ __global__ __launch_bounds__(FNT) void bf_bwd_loop(pkc_rnn_args a, int co) {
 // one tile per workgroup over H / 4 = 256 workgroups — ran 22 us per step: 256 arrivals on one
 // counter and 256 readers of the whole 128 KB h_{t-1} per step.)
 // h_t (fp32) is handed off as in the other loops.
-template <int SL, int TL>
+template <int SL>
 __global__ __launch_bounds__(FNT) void f32_fwd_loop(pkc_rnn_args a) {
-  constexpr int NU = 4;                         // units per tile; TL tiles (4 TL units) per workgroup
+  constexpr int NU = 4, TL = 4;                 // units per tile; tiles (4 TL units) per workgroup
   __shared__ float red[FNW][TL][ROWS][UPW];     // each wave's partial tiles (16 rows x 16 columns)
   __shared__ int abort_flag;
   const RnnIdx ix = mkidx(a);
@@ -781,116 +784,14 @@ __global__ __launch_bounds__(FNT) void f32_fwd_loop(pkc_rnn_args a) {
 }
 
 // BPTT of the same mode: dh_tt[r][k] = sum_g sum_j dgates_g[tt + 1][r][j] U_g[j][k] for the
-// workgroup's 16 columns k and <= 16 rows (blockIdx.y: row block); wave w owns the per-step 8-wave
-// kernel's strip w of j for ALL four gates (U^T strips: 4 SL registers; 16 waves of two gates each
-// would leave 128 registers a wave for 4 SL + 2 SL), each gate's fp32 chain in the per-step order,
-// the gates' dgates_t loaded two at a time (the next gate's strips in flight during a chain), the
-// 8 strips summed as red_sum<8>, the gates as rnn_bwd_epi, then lstm_grads: bit-identical.
-template <int SL>
-__global__ __launch_bounds__(FNT) void f32_bwd_loop(pkc_rnn_args a) {
-  __shared__ float red[4][FNW][ROWS][UPW];      // [gate][strip] partial tiles of the step
-  __shared__ int abort_flag;
-  const RnnIdx ix = mkidx(a);
-  const int H = a.H, B = ix.B2, T = a.T;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 15, q = lane >> 4;
-  const int k0 = blockIdx.x * UPW;
-  const int rb = (B + (int)gridDim.y - 1) / (int)gridDim.y;   // rows per workgroup (<= 16)
-  const int y0 = rb * (int)blockIdx.y;
-  const unsigned nwg = gridDim.x * gridDim.y;
-  const int64_t n = (int64_t)B * H, TB2H = (int64_t)T * B * H;
-  unsigned* ctr = reinterpret_cast<unsigned*>(a.work + 4 * n);
-  const int kb = (4 * w + q) * SL;
-  float vu[4][SL];                              // U^T strips (ut[g][k0 + c][kb ..]) of the loop
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const float* pu = a.ut + (int64_t)g * H * H + (int64_t)(k0 + c) * H + kb;
-#pragma unroll
-    for (int s4 = 0; s4 < SL; s4 += 4) {
-      const float4 v = *reinterpret_cast<const float4*>(pu + s4);
-      vu[g][s4] = v.x; vu[g][s4 + 1] = v.y; vu[g][s4 + 2] = v.z; vu[g][s4 + 3] = v.w;
-    }
-  }
-  const bool ep = tid < rb * UPW && y0 + (tid >> 4) < B;
-  const int r = ep ? y0 + (tid >> 4) : 0, k = k0 + (tid & 15);
-  const int64_t e = (int64_t)r * H + k;
-  const bool rc = c < rb && y0 + c < B;         // this lane's MFMA row y0 + c is one of ours
-  float gcar = a.work[e], dccar = a.work[2 * n + e];   // step T-1's carries (rnn_bwd_init)
-  const float mreg = drop_val(a, r, k, B);
-  const __amdgpu_buffer_rsrc_t dgr = pub_rsrc(a.dgates);
-  const unsigned lo = 4u * (unsigned)((int64_t)(y0 + c) * H + kb);   // this lane's strip in a slab
-  LTR_DECL;
-  for (int tt = T - 2; tt >= 0; --tt) {
-    LTR_MARK(0);
-    const int t = tt + 1;
-    const int64_t si = ix.st(tt, r, k);
-    const float f = a.gates[si], ig = a.gates[TB2H + si], o = a.gates[2 * TB2H + si];
-    const float cc = a.gates[3 * TB2H + si];
-    const float cN = a.cs[(int64_t)(tt + 1) * n + e], cP = a.cs[(int64_t)tt * n + e];
-    const float dyv = dy_at(a, ix.out(tt, r, k));
-    if (tt < T - 2 && !wait_ctr(ctr, nwg * (unsigned)(T - 2 - tt), &abort_flag)) return;
-    LTR_MARK(1);
-    float va[2][SL];
-    auto ld_gate = [&](int g, float* v) {
-      const unsigned off = 4u * (unsigned)(g * TB2H + t * n) + lo;
-#pragma unroll
-      for (int m = 0; m < SL / 4; ++m) ld_pub4(dgr, rc ? off + 16 * m : OOB, v + 4 * m);
-    };
-    ld_gate(0, va[0]);
-    ld_gate(1, va[1]);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s2 = 0; s2 < SL; ++s2)
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(va[g & 1][s2], vu[g][s2], acc, 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) red[g][w][4 * q + i][c] = acc[i];
-      if (g + 2 < 4) {
-        // the chain has read its strips: reuse them for gate g + 2 (kept below the chain, so at
-        // most two gates' strips are live)
-        asm volatile("" ::"v"(acc) : "memory");
-        ld_gate(g + 2, va[g & 1]);
-      }
-    }
-    lds_barrier();
-    LTR_MARK(2);
-    if (ep) {
-      const int kl = tid & 15;
-      float dh = 0.f;                           // rnn_bwd_epi: the gate slabs in order
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        auto p = [&](int v) { return red[g][v][r - y0][kl]; };
-        dh += ((p(0) + p(1)) + (p(2) + p(3))) + ((p(4) + p(5)) + (p(6) + p(7)));
-      }
-      const float g = dyv + dh;                 // bwd_step_epi
-      float dg[4];
-      const float dco = lstm_grads(a.act, f, ig, o, cc, cN, cP, mreg, g, dccar, dg);
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) st_pub(a.dgates + q4 * TB2H + si, dg[q4]);
-      gcar = g;
-      dccar = dco;
-    }
-    LTR_MARK(3);
-    if (tt > 0) arrive(ctr);
-    LTR_MARK(4);
-    LTR_MARK(5);
-  }
-  LTR_STORE(1);
-  if (ep && T > 1) {
-    const int p0 = (T - 1) & 1;
-    a.work[p0 * n + e] = gcar;
-    a.work[2 * n + p0 * n + e] = dccar;
-  }
-}
-
-// The same BPTT with the step's dgates_t staged through LDS (f32_bwd_lds): 8-row blocks
-// (blockIdx.y; 4 H / 16 workgroups for C4), the block's rows of all four gates (4 x 8 x H fp32,
-// 128 KB at H = 1024) loaded in ONE round trip — 16-byte sc1 loads to registers, every lane 16 of
-// them, then written to LDS — instead of f32_bwd_loop's two dependent round trips (its registers
-// hold only two gates' strips beside the four gates' U^T).  The chains read their A strips from
-// LDS: same operands, same order, bit-identical.  LDS rows padded by 4 floats.
+// workgroup's 16 columns k and 8 rows (blockIdx.y: row block; 4 H / 16 workgroups for C4); wave w
+// owns the per-step 8-wave kernel's strip w of j for ALL four gates (U^T strips: 4 SL registers),
+// each gate's fp32 chain in the per-step order, the 8 strips summed as red_sum<8>, the gates as
+// rnn_bwd_epi, then lstm_grads: bit-identical.  The step's dgates_t is staged through LDS: the
+// block's rows of all four gates (4 x 8 x H fp32, 128 KB at H = 1024) are loaded in ONE round
+// trip — 16-byte sc1 loads to registers, every lane 16 of them, then written to LDS — and the
+// chains read their A strips from there (a register form that held two gates' strips beside U^T
+// needed two dependent round trips per step and lost).  LDS rows padded by 4 floats.
 constexpr int LRB = 8;                          // rows per workgroup
 template <int SL>
 __global__ __launch_bounds__(FNT) void f32_bwd_lds(pkc_rnn_args a) {
@@ -1208,11 +1109,8 @@ __global__ __launch_bounds__(64 * GW) void lg_bwd_loop(pkc_rnn_args a) {
 
 }  // namespace lstmp
 
-static int device_cus();
-
 bool rnn_lstm_persist_ok(const pkc_rnn_args* a, bool bwd) {
-  const char* env = getenv("PKC_RNN_LSTM_PERSIST");   // "0": the per-step launches (A/B, tests)
-  if (env && env[0] == '0') return false;
+  if (!env_flag("PKC_RNN_LSTM_PERSIST", true)) return false;   // 0: the per-step launches
   if (a->cell != PKC_CELL_LSTM || a->ln_gamma || a->kmap_fwd || a->kmap_bwd || !a->work) return false;
   if (a->H / lstmp::UPW > device_cus()) return false;   // (every workgroup resident: one per CU)
   if ((int64_t)4 * (a->bidir ? 2 * a->B : a->B) * a->H < lstmp::CTR_FLOATS) return false;
@@ -1232,10 +1130,11 @@ bool rnn_lstm_persist_ok(const pkc_rnn_args* a, bool bwd) {
     return a->U_h[0] && a->U_h[1] && a->U_h[2] && a->U_h[3];
   }
   if (a->qbits <= 0) {                          // exact fp32 step products (C4 fp32)
-    const char* f32 = getenv("PKC_RNN_LSTM_F32");   // "0": the per-step launches
-    if (f32 && f32[0] == '0') return false;
+    if (!env_flag("PKC_RNN_LSTM_F32", true)) return false;   // 0: the per-step launches
     if (B2 > lstmp::R32 || a->H % 256 || a->H < 512 || a->H > 1024) return false;
-    if (a->H / 16 * ((B2 + 15) / 16) > device_cus()) return false;   // (co-residency)
+    // co-residency of the launch's grid: row blocks of 16 (forward), of LRB = 8 (BPTT)
+    const int rows = bwd ? lstmp::LRB : lstmp::ROWS;
+    if (a->H / lstmp::UPW * ((B2 + rows - 1) / rows) > device_cus()) return false;
     if (bwd) return a->dgates && a->ut;
     return a->U[0] && a->U[1] && a->U[2] && a->U[3];
   }
@@ -1246,22 +1145,10 @@ bool rnn_lstm_persist_ok(const pkc_rnn_args* a, bool bwd) {
 // default (C4 bf16 19.9-20.0 vs 20.9-21.0 us per step-layer, same box; the bf16 sums of an
 // element in another grouping: tests/test_gpu_steps.py holds every time step to the oracle), the
 // per-step kernels' chunking with PKC_RNN_LSTM_CO=0 (bit-identical to the per-step launches)
-static int lstm_bf16_coalesced() {
-  const char* v = getenv("PKC_RNN_LSTM_CO");
-  return v && v[0] == '0' ? 0 : 1;
-}
+static int lstm_bf16_coalesced() { return env_flag("PKC_RNN_LSTM_CO", true) ? 1 : 0; }
 
-// Compute units of the current device: a grid-synchronised loop needs every workgroup resident at
-// once, and these workgroups (512-1024 threads, large register files) are sized for one per CU, so
-// a row split is only taken while the whole grid still fits one workgroup per CU.
-static int device_cus() {
-  int dev = 0, n = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-    return 256;
-  return n;
-}
-// the largest of rs, rs / 2, ..., 1 whose grid (base workgroups x split) fits the device
+// the largest of rs, rs - 1, ..., 1 whose grid (base workgroups x split) fits the device: a row
+// split is only taken while the whole grid still fits one workgroup per CU
 static int fit_split(int rs, int base) {
   const int cus = device_cus();
   while (rs > 1 && base * rs > cus) rs = rs > 2 ? rs - 1 : 1;
@@ -1269,21 +1156,16 @@ static int fit_split(int rs, int base) {
 }
 
 // bf16 loops with more than 16 rows (C4: 2 x 16): the workgroups per unit block the rows are
-// split over (PKC_RNN_LSTM_RS = 1, 2 or 4 for the forward loop, default 2; 1 keeps both 16-row
-// chains in one workgroup; PKC_RNN_LSTM_RS_BWD for the BPTT loop, default 4)
-static int lstm_bf16_rows_split(const pkc_rnn_args* a, bool bwd = false) {
-  auto knob = [](const char* name, int dflt) {
-    const char* v = getenv(name);
-    const int x = v ? atoi(v) : dflt;
-    return x == 1 || x == 2 || x == 4 ? x : dflt;
-  };
-  static const int rs = knob("PKC_RNN_LSTM_RS", 2);
-  // (the BPTT's default is 4 row blocks: with the sharded step counter the 256-workgroup BPTT
-  // measured 13.56 vs 14.83-14.89 us per step-layer at C4, profiles/r06_c4_bf16_bwd_rows_split_ab.txt)
-  static const int rsb = knob("PKC_RNN_LSTM_RS_BWD", 4);
+// split over.  Forward: PKC_RNN_LSTM_RS = 1 or 2, default 2.  BPTT: PKC_RNN_LSTM_RS_BWD = 1 or 4,
+// default 4 — with the sharded step counter the 256-workgroup BPTT measured 13.56 vs 14.83-14.89 us
+// per step-layer at C4, profiles/r06_c4_bf16_bwd_rows_split_ab.txt.  1 keeps both 16-row chains in
+// one workgroup, and is what a split that does not fit the device falls back to.
+static int lstm_bf16_rows_split(const pkc_rnn_args* a, bool bwd) {
+  static const int rs = env_int("PKC_RNN_LSTM_RS", 2) == 1 ? 1 : 2;
+  static const int rsb = env_int("PKC_RNN_LSTM_RS_BWD", 4) == 1 ? 1 : 4;
   if ((a->bidir ? 2 * a->B : a->B) <= 16) return 1;
-  const int r = fit_split(bwd ? rsb : rs, a->H / lstmp::UPW);
-  return r == 3 ? 2 : r;                        // (the bf16 loops take 1, 2 or 4)
+  const int want = bwd ? rsb : rs;
+  return a->H / lstmp::UPW * want <= device_cus() ? want : 1;
 }
 
 // QX BPTT loop: workgroups per column block the B rows are split over (PKC_RNN_LSTM_QX_RS, default
@@ -1291,8 +1173,7 @@ static int lstm_bf16_rows_split(const pkc_rnn_args* a, bool bwd = false) {
 // profiles/r06_c5_qx_bwd_rows_split_sharded_ab.txt; 1: all rows in one workgroup)
 static int lstm_qx_bwd_rows_split(const pkc_rnn_args* a) {
   static const int rs = [] {
-    const char* v = getenv("PKC_RNN_LSTM_QX_RS");
-    const int x = v ? atoi(v) : 4;
+    const int x = env_int("PKC_RNN_LSTM_QX_RS", 4);
     return x >= 1 && x <= 4 ? x : 4;
   }();
   return a->B > 8 ? fit_split(rs, a->H / lstmp::UPW) : 1;
@@ -1300,8 +1181,7 @@ static int lstm_qx_bwd_rows_split(const pkc_rnn_args* a) {
 
 // liGRU exact-fp32 step mode in the grid-synchronised loops (lg_fwd_loop / lg_bwd_loop)
 bool rnn_ligru_grid_ok(const pkc_rnn_args* a, bool bwd) {
-  const char* env = getenv("PKC_RNN_LIGRU_GRID");     // "0": the per-step launches
-  if (env && env[0] == '0') return false;
+  if (!env_flag("PKC_RNN_LIGRU_GRID", true)) return false;   // 0: the per-step launches
   const int64_t B2 = a->bidir ? 2 * a->B : a->B;
   if (a->cell != PKC_CELL_LIGRU || a->step_bf16 || a->qbits > 0 || a->ln_gamma || !a->work ||
       B2 > lstmp::ROWS || a->H > lstmp::GKMAX)
@@ -1312,47 +1192,11 @@ bool rnn_ligru_grid_ok(const pkc_rnn_args* a, bool bwd) {
   return bwd ? (a->dgates && a->ut) : true;
 }
 
-// fp32 LSTM BPTT loop: row blocks per column block (each <= 16 rows, the MFMA tile;
-// PKC_RNN_LSTM_F32_RS raises the count, e.g. 4 for 8-row blocks), bounded by co-residency
-static int lstm_f32_bwd_rows_split(const pkc_rnn_args* a, int B2) {
-  static const int rs = [] {
-    const char* v = getenv("PKC_RNN_LSTM_F32_RS");
-    const int x = v ? atoi(v) : 0;
-    return x >= 1 && x <= 4 ? x : 0;
-  }();
-  const int need = (B2 + lstmp::ROWS - 1) / lstmp::ROWS;
-  const int want = rs > need ? rs : need;
-  const int r = fit_split(want, a->H / lstmp::UPW);
-  return r < need ? need : r;
-}
-
-// fp32 LSTM forward loop: 16-column tiles per workgroup (PKC_RNN_LSTM_F32_TL = 2 or 4), 2 only
-// while the grid (H / 8 x row blocks) keeps one workgroup per CU
-static int lstm_f32_fwd_tiles(const pkc_rnn_args* a, int row_blocks) {
-  static const int tl = [] {
-    const char* v = getenv("PKC_RNN_LSTM_F32_TL");
-    return v && atoi(v) == 2 ? 2 : 4;
-  }();
-  return tl == 2 && a->H / 8 * row_blocks <= device_cus() ? 2 : 4;
-}
-
-// fp32 LSTM BPTT with the dgates block staged in LDS (f32_bwd_lds; PKC_RNN_LSTM_F32_LDS=0: the
-// register form f32_bwd_loop), when its 8-row blocks keep the grid at one workgroup per CU
-static bool lstm_f32_bwd_lds(const pkc_rnn_args* a) {
-  static const bool on = [] {
-    const char* v = getenv("PKC_RNN_LSTM_F32_LDS");
-    return !(v && v[0] == '0');
-  }();
-  const int B2 = a->bidir ? 2 * a->B : a->B;
-  return on && a->H / lstmp::UPW * ((B2 + lstmp::LRB - 1) / lstmp::LRB) <= device_cus();
-}
-
 // liGRU grid loops: workgroups per unit block the B2 rows are split over (PKC_RNN_LIGRU_GRID_RS,
 // default 2 when B2 > 8; 1: all rows in one workgroup)
 static int ligru_grid_rows_split(const pkc_rnn_args* a) {
   static const int rs = [] {
-    const char* v = getenv("PKC_RNN_LIGRU_GRID_RS");
-    const int x = v ? atoi(v) : 2;
+    const int x = env_int("PKC_RNN_LIGRU_GRID_RS", 2);
     return x >= 1 && x <= 4 ? x : 2;
   }();
   // (the forward's unit blocks are the larger grid: ceil(H / 8))
@@ -1366,46 +1210,40 @@ static int lstm_ctr_reset(const pkc_rnn_args* a, hipStream_t s) {
   return PKC_OK;
 }
 
+// one launch of a loop kernel at kc = H / 256 in {2, 3, 4}: K(kc) names the instance
+#define PKC_KC(K, GRID, NT_, ...)                                                    \
+  do {                                                                              \
+    if (kc == 2) hipLaunchKernelGGL((K(2)), GRID, dim3(NT_), 0, s, __VA_ARGS__);    \
+    else if (kc == 3) hipLaunchKernelGGL((K(3)), GRID, dim3(NT_), 0, s, __VA_ARGS__); \
+    else hipLaunchKernelGGL((K(4)), GRID, dim3(NT_), 0, s, __VA_ARGS__);            \
+  } while (0)
+
 int rnn_lstm_persist_fwd(const pkc_rnn_args* a, hipStream_t s) {
   using namespace lstmp;
   int st = lstm_ctr_reset(a, s);
   if (st) return st;
-  const dim3 grid(a->H / UPW);
+  const int B2 = a->bidir ? 2 * a->B : a->B;
   const int kc = a->H / 256;
+  const unsigned gx = a->H / UPW;
   if (a->qh_exact) {
-    if (kc == 2) hipLaunchKernelGGL(qx_fwd_loop<2>, grid, dim3(FNT), 0, s, *a);
-    else if (kc == 3) hipLaunchKernelGGL(qx_fwd_loop<3>, grid, dim3(FNT), 0, s, *a);
-    else hipLaunchKernelGGL(qx_fwd_loop<4>, grid, dim3(FNT), 0, s, *a);
-  } else if (!a->step_bf16) {                   // exact fp32 step products: 4 units per workgroup
-    const int B2 = a->bidir ? 2 * a->B : a->B;
-    const int ry = lstm_f32_bwd_rows_split(a, B2);              // row blocks of <= 16
-    if (lstm_f32_fwd_tiles(a, ry) == 2) {                        // 8 units per workgroup
-      const dim3 g8(a->H / 8, ry);
-      if (kc == 2) hipLaunchKernelGGL((f32_fwd_loop<16, 2>), g8, dim3(FNT), 0, s, *a);
-      else if (kc == 3) hipLaunchKernelGGL((f32_fwd_loop<24, 2>), g8, dim3(FNT), 0, s, *a);
-      else hipLaunchKernelGGL((f32_fwd_loop<32, 2>), g8, dim3(FNT), 0, s, *a);
-    } else {
-      const dim3 g16(a->H / 16, ry);
-      if (kc == 2) hipLaunchKernelGGL((f32_fwd_loop<16, 4>), g16, dim3(FNT), 0, s, *a);
-      else if (kc == 3) hipLaunchKernelGGL((f32_fwd_loop<24, 4>), g16, dim3(FNT), 0, s, *a);
-      else hipLaunchKernelGGL((f32_fwd_loop<32, 4>), g16, dim3(FNT), 0, s, *a);
-    }
+#define PKC_K(KC) qx_fwd_loop<KC>
+    PKC_KC(PKC_K, dim3(gx), FNT, *a);
+#undef PKC_K
+  } else if (!a->step_bf16) {                   // exact fp32 step products: row blocks of <= 16
+#define PKC_K(KC) f32_fwd_loop<8 * KC>
+    PKC_KC(PKC_K, dim3(gx, (B2 + ROWS - 1) / ROWS), FNT, *a);
+#undef PKC_K
   } else {
     const int co = lstm_bf16_coalesced();
-    const int rs = lstm_bf16_rows_split(a);
-    if (rs == 4) {
-      const dim3 g4(grid.x, 4);
-      if (kc == 2) hipLaunchKernelGGL((bf_fwd_loop<2, 4>), g4, dim3(FNT), 0, s, *a, co);
-      else if (kc == 3) hipLaunchKernelGGL((bf_fwd_loop<3, 4>), g4, dim3(FNT), 0, s, *a, co);
-      else hipLaunchKernelGGL((bf_fwd_loop<4, 4>), g4, dim3(FNT), 0, s, *a, co);
-    } else if (rs == 2) {
-      const dim3 g2(grid.x, 2);
-      if (kc == 2) hipLaunchKernelGGL((bf_fwd_loop<2, 2>), g2, dim3(FNT), 0, s, *a, co);
-      else if (kc == 3) hipLaunchKernelGGL((bf_fwd_loop<3, 2>), g2, dim3(FNT), 0, s, *a, co);
-      else hipLaunchKernelGGL((bf_fwd_loop<4, 2>), g2, dim3(FNT), 0, s, *a, co);
-    } else if (kc == 2) hipLaunchKernelGGL((bf_fwd_loop<2, 1>), grid, dim3(FNT), 0, s, *a, co);
-    else if (kc == 3) hipLaunchKernelGGL((bf_fwd_loop<3, 1>), grid, dim3(FNT), 0, s, *a, co);
-    else hipLaunchKernelGGL((bf_fwd_loop<4, 1>), grid, dim3(FNT), 0, s, *a, co);
+    if (lstm_bf16_rows_split(a, false) == 2) {
+#define PKC_K(KC) bf_fwd_loop<KC, 2>
+      PKC_KC(PKC_K, dim3(gx, 2), FNT, *a, co);
+#undef PKC_K
+    } else {
+#define PKC_K(KC) bf_fwd_loop<KC, 1>
+      PKC_KC(PKC_K, dim3(gx), FNT, *a, co);
+#undef PKC_K
+    }
   }
   PKC_LAUNCH_CHECK("pkc_rnn_fwd persistent LSTM loop");
   return PKC_OK;
@@ -1439,46 +1277,46 @@ int rnn_lstm_persist_bwd(const pkc_rnn_args* a, hipStream_t s) {
   if (a->T < 2) return PKC_OK;
   int st = lstm_ctr_reset(a, s);
   if (st) return st;
-  const dim3 grid(a->H / UPW);
+  const int B2 = a->bidir ? 2 * a->B : a->B;
   const int kc = a->H / 256;
+  const unsigned gx = a->H / UPW;
   if (a->qh_exact) {
-    const char* x3 = getenv("PKC_RNN_LSTM_PERSIST_X3");   // "0": the fp32 chains (bit-identical)
-    const dim3 gq(grid.x, lstm_qx_bwd_rows_split(a));
-    if (x3 && x3[0] == '0') hipLaunchKernelGGL(bwd_loop<false>, gq, dim3(BNT), 0, s, *a);
-    else hipLaunchKernelGGL(bwd_loop<true>, gq, dim3(BNT), 0, s, *a);
-  }
-  else if (!a->step_bf16 && lstm_f32_bwd_lds(a)) {   // exact fp32, dgates staged in LDS
-    const int B2 = a->bidir ? 2 * a->B : a->B;
-    const dim3 gl(grid.x, (B2 + LRB - 1) / LRB);
-    if (kc == 2) hipLaunchKernelGGL(f32_bwd_lds<16>, gl, dim3(FNT), 0, s, *a);
-    else if (kc == 3) hipLaunchKernelGGL(f32_bwd_lds<24>, gl, dim3(FNT), 0, s, *a);
-    else hipLaunchKernelGGL(f32_bwd_lds<32>, gl, dim3(FNT), 0, s, *a);
-  }
-  else if (!a->step_bf16) {                     // exact fp32: rows in blocks of <= 16
-    const int B2 = a->bidir ? 2 * a->B : a->B;
-    const dim3 gf(grid.x, lstm_f32_bwd_rows_split(a, B2));
-    if (kc == 2) hipLaunchKernelGGL(f32_bwd_loop<16>, gf, dim3(FNT), 0, s, *a);
-    else if (kc == 3) hipLaunchKernelGGL(f32_bwd_loop<24>, gf, dim3(FNT), 0, s, *a);
-    else hipLaunchKernelGGL(f32_bwd_loop<32>, gf, dim3(FNT), 0, s, *a);
+    const dim3 gq(gx, lstm_qx_bwd_rows_split(a));
+    // PKC_RNN_LSTM_PERSIST_X3=0: the fp32 chains (bit-identical to the per-step launches)
+    if (env_flag("PKC_RNN_LSTM_PERSIST_X3", true))
+      hipLaunchKernelGGL(bwd_loop<true>, gq, dim3(BNT), 0, s, *a);
+    else
+      hipLaunchKernelGGL(bwd_loop<false>, gq, dim3(BNT), 0, s, *a);
+  } else if (!a->step_bf16) {                   // exact fp32: 8-row blocks staged in LDS
+#define PKC_K(KC) f32_bwd_lds<8 * KC>
+    PKC_KC(PKC_K, dim3(gx, (B2 + LRB - 1) / LRB), FNT, *a);
+#undef PKC_K
   } else {
     const int co = lstm_bf16_coalesced();
-    const int rs = lstm_bf16_rows_split(a, true);
-    if (rs == 4) {
-      const dim3 g4(grid.x, 4);
-      if (kc == 2) hipLaunchKernelGGL((bf_bwd_loop<2, 4>), g4, dim3(FNT), 0, s, *a, co);
-      else if (kc == 3) hipLaunchKernelGGL((bf_bwd_loop<3, 4>), g4, dim3(FNT), 0, s, *a, co);
-      else hipLaunchKernelGGL((bf_bwd_loop<4, 4>), g4, dim3(FNT), 0, s, *a, co);
-    } else if (rs == 2) {
-      const dim3 g2(grid.x, 2);
-      if (kc == 2) hipLaunchKernelGGL((bf_bwd_loop<2, 2>), g2, dim3(FNT), 0, s, *a, co);
-      else if (kc == 3) hipLaunchKernelGGL((bf_bwd_loop<3, 2>), g2, dim3(FNT), 0, s, *a, co);
-      else hipLaunchKernelGGL((bf_bwd_loop<4, 2>), g2, dim3(FNT), 0, s, *a, co);
-    } else if (kc == 2) hipLaunchKernelGGL((bf_bwd_loop<2, 1>), grid, dim3(FNT), 0, s, *a, co);
-    else if (kc == 3) hipLaunchKernelGGL((bf_bwd_loop<3, 1>), grid, dim3(FNT), 0, s, *a, co);
-    else hipLaunchKernelGGL((bf_bwd_loop<4, 1>), grid, dim3(FNT), 0, s, *a, co);
+    if (lstm_bf16_rows_split(a, true) == 4) {
+#define PKC_K(KC) bf_bwd_loop<KC, 4>
+      PKC_KC(PKC_K, dim3(gx, 4), FNT, *a, co);
+#undef PKC_K
+    } else {
+#define PKC_K(KC) bf_bwd_loop<KC, 1>
+      PKC_KC(PKC_K, dim3(gx), FNT, *a, co);
+#undef PKC_K
+    }
   }
   PKC_LAUNCH_CHECK("pkc_rnn_bwd persistent LSTM loop");
   return PKC_OK;
+}
+#undef PKC_KC
+
+// The form of the recurrent time loop for these arguments — the one decision pkc_rnn_fwd /
+// pkc_rnn_bwd dispatch on and pkc_rnn_persist_form reports: 0 one launch per step, 1 the persistent
+// liGRU loops (pkc_rnn_persist.hip), 2 the grid-synchronised LSTM loops, 3 the grid-synchronised
+// liGRU loops.
+int rnn_loop_form(const pkc_rnn_args* a, bool bwd) {
+  if (a->cell == PKC_CELL_LIGRU && rnn_persist_ok(a, bwd)) return 1;
+  if (rnn_lstm_persist_ok(a, bwd)) return 2;
+  if (rnn_ligru_grid_ok(a, bwd)) return 3;
+  return 0;
 }
 
 }  // namespace pkc
@@ -1493,10 +1331,9 @@ extern "C" int pkc_trace_read_lstm_persist(unsigned long long* host, int n) {
 #endif
 
 // which time-loop form pkc_rnn_fwd / pkc_rnn_bwd takes for these arguments: 1 the persistent liGRU
-// loops, 2 the persistent LSTM loops, 0 one launch per step
+// loops, 2 the grid-synchronised loops (LSTM or liGRU), 0 one launch per step
 extern "C" int pkc_rnn_persist_form(const pkc_rnn_args* a, int bwd) {
   if (!a) return 0;
-  if (a->cell == PKC_CELL_LIGRU && pkc::rnn_persist_ok(a, bwd != 0)) return 1;
-  if (pkc::rnn_lstm_persist_ok(a, bwd != 0) || pkc::rnn_ligru_grid_ok(a, bwd != 0)) return 2;
-  return 0;
+  const int form = pkc::rnn_loop_form(a, bwd != 0);
+  return form == 3 ? 2 : form;
 }

@@ -707,7 +707,6 @@ class Engine:
         # on the device after each such launch, raised at the next host sync (loss_values /
         # chunk_totals) instead of passing on a half-computed layer
         self.loop_fail = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        self._loop_forms = {}
 
     # ------------------------------------------------------------------ graph construction
     def _build_graph(self):
@@ -2950,11 +2949,9 @@ class Engine:
 
     def _loop_watch(self, ra, lb, bwd):
         """After a layer's pkc_rnn_fwd / pkc_rnn_bwd: when it ran as a grid-synchronised loop,
-        add its timeout word (rwork[4 B2 H + 1], zeroed by the launch) to loop_fail."""
-        key = (id(lb), bwd, ra.T)
-        form = self._loop_forms.get(key)
-        if form is None:
-            form = self._loop_forms[key] = L.lib().pkc_rnn_persist_form(C.byref(ra), int(bwd))
+        add its timeout word (rwork[4 B2 H + 1], zeroed by the launch) to loop_fail.  The form is
+        asked of the library each time: the query is the dispatch's own decision function."""
+        form = L.lib().pkc_rnn_persist_form(C.byref(ra), int(bwd))
         if form == 2 and not (bwd and ra.T < 2):
             o = 4 * lb["B2"] * lb["H"] + 1
             self.loop_fail.add_(lb["rwork"][o:o + 1].view(torch.int32))

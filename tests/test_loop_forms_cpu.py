@@ -82,6 +82,17 @@ def test_per_step_fallbacks(case):
 
 def test_environment_switches(monkeypatch):
     from pkc import _lib as L
+    # removed switches of retired kernel forms: setting them changes nothing
+    for name, value in (("PKC_RNN_LSTM_F32_TL", "2"), ("PKC_RNN_LSTM_F32_LDS", "0"),
+                        ("PKC_RNN_LSTM_F32_RS", "4")):
+        monkeypatch.setenv(name, value)
+        assert _form(_args(L.CELL_LSTM, 1024, 16, True)) == (2, 2)
+        assert _form(_args(L.CELL_LSTM, 512, 12, False)) == (2, 2)
+        assert _form(_args(L.CELL_LSTM, 768, 10, True)) == (2, 2)
+        assert _form(_args(L.CELL_LSTM, 1024, 17, True)) == (0, 0)
+    monkeypatch.setenv("PKC_RNN_LSTM_RS", "4")           # no longer a value of this switch
+    assert _form(_args(L.CELL_LSTM, 1024, 16, True, step_bf16=1, hs_h=True, U_h=True,
+                       ut_h=True, dgates_h=True)) == (2, 2)
     monkeypatch.setenv("PKC_RNN_LSTM_F32", "0")          # the fp32 LSTM loops only
     assert _form(_args(L.CELL_LSTM, 1024, 16, True)) == (0, 0)
     assert _form(_args(L.CELL_LSTM, 1024, 16, True, step_bf16=1, hs_h=True, U_h=True,
