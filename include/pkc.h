@@ -245,6 +245,15 @@ typedef struct {
 } pkc_nll_args;
 int pkc_nll_fused(const pkc_nll_args* a, void* stream);
 
+/* mse cost (utils.py:2045-2048: torch.mean((y - target) ** 2) over all M x N elements) and its
+ * backward in one pass: row_loss[r] = (1/N) sum_j (y[r,j] - target[r,j])^2, so that mean_r row_loss
+ * is the cost and pkc_loss_finalize takes it as one more term; dy[r,j] = weight * 2/(M*N) *
+ * (y[r,j] - target[r,j]) (dy == NULL: the loss only).  One wave per row and a fixed reduction tree:
+ * reruns are bit-identical.  16-byte loads where every pointer and leading dimension allows them,
+ * scalar otherwise (a target that is a column range of the batch buffer). */
+int pkc_mse_fused(int M, int N, const float* y, int64_t ldy, const float* target, int64_t ldt,
+                  float weight, float* dy, int64_t lddy, float* row_loss, void* stream);
+
 /* LogSoftmax backward for an upstream gradient dy (M x N, row-major): dz = dy - exp(logp) *
  * rowsum(dy).  The architecture plug-in's trainable head forward (neural_networks.py:73-74 under
  * the reference's autograd, core.py:221-232); dz may alias dy. */

@@ -385,6 +385,43 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(int nheads, const fl
   loss_finalize_body(nheads, rl, w, M, rerr, out, acc, advance);
 }
 
+// mse cost (utils.py:2045-2048: torch.mean((a - b) ** 2)) with its autograd backward in the same
+// pass: one wave per row, lanes stride over the columns, the row's squares summed by the fixed
+// shuffle tree (no atomics: reruns are bit-identical).  c = weight * 2 / (M * N), rounded once on
+// the host.  VEC: whole float4 column chunks of 16-byte aligned rows.
+template <bool VEC>
+__global__ __launch_bounds__(64 * LW) void mse_kernel(int M, int N, const float* __restrict__ y,
+                                                      int64_t ldy, const float* __restrict__ t,
+                                                      int64_t ldt, float c, float* __restrict__ dy,
+                                                      int64_t lddy, float* __restrict__ row_loss) {
+  const int r = blockIdx.x * LW + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (r >= M) return;
+  const float* yr = y + (int64_t)r * ldy;
+  const float* tr = t + (int64_t)r * ldt;
+  float* dr = dy ? dy + (int64_t)r * lddy : nullptr;
+  float s = 0.f;
+  if (VEC) {
+    for (int j = 4 * lane; j < N; j += 256) {
+      const float4 a = *reinterpret_cast<const float4*>(yr + j);
+      const float4 b = *reinterpret_cast<const float4*>(tr + j);
+      const float4 d = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
+      s = fmaf(d.x, d.x, s);
+      s = fmaf(d.y, d.y, s);
+      s = fmaf(d.z, d.z, s);
+      s = fmaf(d.w, d.w, s);
+      if (dr) *reinterpret_cast<float4*>(dr + j) = make_float4(c * d.x, c * d.y, c * d.z, c * d.w);
+    }
+  } else {
+    for (int j = lane; j < N; j += 64) {
+      const float d = yr[j] - tr[j];
+      s = fmaf(d, d, s);
+      if (dr) dr[j] = c * d;
+    }
+  }
+  s = warp_sum(s);
+  if (lane == 0) row_loss[r] = s / (float)N;
+}
+
 }  // namespace pkc
 
 // the 16-byte form: whole float4 column chunks, aligned rows (the scalar form otherwise)
@@ -476,6 +513,30 @@ extern "C" int pkc_loss_finalize(int nheads, const float* const* row_loss, const
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, S(stream), nheads, row_loss,
                      weights, M, row_err, out, acc, advance_ctr);
   PKC_LAUNCH_CHECK("pkc_loss_finalize");
+  return PKC_OK;
+}
+
+extern "C" int pkc_mse_fused(int M, int N, const float* y, int64_t ldy, const float* target,
+                             int64_t ldt, float weight, float* dy, int64_t lddy, float* row_loss,
+                             void* stream) {
+  using namespace pkc;
+  PKC_CHECK_ARG(M >= 1 && N >= 1, "pkc_mse_fused: M = %d, N = %d (both >= 1)", M, N);
+  PKC_CHECK_ARG(y && target && row_loss, "pkc_mse_fused: null y, target or row_loss");
+  PKC_CHECK_ARG(ldy >= N && ldt >= N && (!dy || lddy >= N),
+                "pkc_mse_fused: a leading dimension (ldy %lld, ldt %lld, lddy %lld) below N = %d",
+                (long long)ldy, (long long)ldt, (long long)lddy, N);
+  const float c = (float)((double)weight * 2.0 / ((double)M * (double)N));
+  auto al = [](const void* p) { return ((uintptr_t)p % 16) == 0; };
+  const bool v4 = N % 4 == 0 && ldy % 4 == 0 && ldt % 4 == 0 && (!dy || lddy % 4 == 0) && al(y) &&
+                  al(target) && al(dy);
+  const dim3 grid((M + LW - 1) / LW), blk(64 * LW);
+  if (v4)
+    hipLaunchKernelGGL(mse_kernel<true>, grid, blk, 0, S(stream), M, N, y, ldy, target, ldt, c, dy,
+                       lddy, row_loss);
+  else
+    hipLaunchKernelGGL(mse_kernel<false>, grid, blk, 0, S(stream), M, N, y, ldy, target, ldt, c, dy,
+                       lddy, row_loss);
+  PKC_LAUNCH_CHECK("pkc_mse_fused");
   return PKC_OK;
 }
 

@@ -187,6 +187,7 @@ _SIGS = {
     "pkc_loss_finalize": (C.c_int, [C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
     "pkc_nll_fused_multi": (C.c_int, [vp, C.c_int, vp]),
     "pkc_logsoftmax_bwd": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp]),
+    "pkc_mse_fused": (C.c_int, [C.c_int, C.c_int, vp, i64, vp, i64, C.c_float, vp, i64, vp, vp]),
     "pkc_colsum": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, i64, vp, C.c_int, vp]),
     "pkc_optim_step": (C.c_int, [vp, C.c_int, vp, C.c_int, vp]),
     "pkc_optim_chunks": (C.c_int, [C.POINTER(i64), C.c_int, C.POINTER(C.c_int32), C.c_int]),

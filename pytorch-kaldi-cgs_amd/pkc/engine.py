@@ -169,6 +169,17 @@ class RegTerm:
         return items, bstart
 
 
+class MseTerm:
+    """One mse line of the [model] (utils.py:2045-2048: torch.mean((a - b) ** 2)) between a
+    feed-forward node's output and a feature stream of the chunk: a loss term whose per-row loss
+    is the row's mean square (pkc_mse_fused), and one more gradient source of its node."""
+    head = False
+
+    def __init__(self, node, c0, name):
+        self.node, self.c0, self.name = node, c0, name
+        self.loss_weight = 0.0
+
+
 def resolve_concat(lines, fea_cols):
     """[model] concatenate(a, b) (utils.py:2014-2016: torch.cat along the feature axis) of feature
     streams — or of earlier such concatenations — whose column ranges are adjacent in the chunk
@@ -780,7 +791,7 @@ class Engine:
                 if lay.head and i != len(net.dnn_lay) - 1:
                     raise NotImplementedError("softmax only as the last layer of an MLP")
             produced[out] = prev[1]
-        scal, self.err_layer = {}, None
+        scal, self.err_layer, mse_terms = {}, None, []
         for out, op, a, b in self.lines:
             if op == "cost_nll":
                 lay = produced[a]
@@ -849,13 +860,40 @@ class Engine:
                     term = RegTerm(op, b, 0, params)
                 term.masks = masks
                 scal[out] = {term: 1.0}
+            elif op == "mse":
+                if a in produced and b in produced:
+                    raise NotImplementedError("mse(%s,%s): an mse between two produced outputs is "
+                                              "not on the pkc path (one side must be a feature "
+                                              "stream)" % (a, b))
+                if a in produced and b in self.fea_cols:
+                    lay, fea = produced[a], b
+                elif b in produced and a in self.fea_cols:
+                    lay, fea = produced[b], a
+                else:
+                    raise ValueError("mse(%s,%s) needs one produced output and one feature stream"
+                                     % (a, b))
+                if type(lay) is not Layer:
+                    raise NotImplementedError("mse on the output of %s: a recurrent, convolution "
+                                              "or normalisation node's output directly is not on "
+                                              "the pkc path" % lay.name)
+                if lay.head:
+                    raise NotImplementedError("mse on the LogSoftmax head %s is not on the pkc path"
+                                              % lay.name)
+                c0, c1 = self.fea_cols[fea]
+                if lay.N != c1 - c0:
+                    raise ValueError("mse(%s,%s): the output is %d wide, the feature stream %d"
+                                     % (a, b, lay.N, c1 - c0))
+                term = MseTerm(lay, c0, out)
+                mse_terms.append(term)
+                scal[out] = {term: 1.0}
             elif op in ("compute", "concatenate"):     # (concatenate: resolve_concat)
                 continue
             else:
                 raise NotImplementedError("[model] operation %s is not on the pkc path" % op)
         for n in self.nodes:
             if getattr(n, "rec_consumer", None) is not None and n.consumers:
-                # its gradient would be the recurrent dX slabs AND the other consumers' slabs
+                # its gradient would be the recurrent dX slabs AND the other consumers' slabs (an
+                # mse term on it is fine: that writes one more slab beside the recurrent ones)
                 raise NotImplementedError("%s: read by a recurrent arch and by other archs" % n.name)
         self.produced = produced
         self.heads = [l for l in self.nodes if l.head]
@@ -865,6 +903,15 @@ class Engine:
             lay.loss_weight = w
         self.reg_terms = [t for t in scal.get("loss_final", {}) if isinstance(t, RegTerm)
                           and t.loss_weight != 0.0]
+        # every mse term is a loss term (weight 0 when loss_final does not hold it); those with a
+        # weight are gradient sources of their node: one slab each in front of the node's other
+        # gradient slabs (its consumers' dX slabs, or a recurrent consumer's layer-0 dX slabs)
+        self.mse_terms = mse_terms
+        if mse_terms and self.external:
+            raise NotImplementedError("mse in the external mode (there the loss is the caller's)")
+        for n in self.nodes:
+            n.mse_grad = [t for t in mse_terms if t.node is n and t.loss_weight != 0.0
+                          and self.train]
         if self.err_layer is None and self.heads:
             self.err_layer = self.heads[0]
         for lay in self.nodes:
@@ -949,7 +996,8 @@ class Engine:
             ent["buf"] = _f32(ent["Q"] * M * width, dev)
             ent["work"] = _f32(256, dev)
         for n in self.nodes:
-            cap = 0
+            # (a recurrent consumer's layer-0 dX buffer holds the mse slabs otherwise, _alloc_rec)
+            cap = 0 if getattr(n, "rec_consumer", None) is not None else len(n.mse_grad)
             for c in n.consumers:
                 # an input norm (no matmul) writes its input gradient into one slab
                 c.sxcap = 1 if c.W is None else (self.cap or _splits(
@@ -960,7 +1008,8 @@ class Engine:
         for n in reversed(self.nodes):
             rc = getattr(n, "rec_consumer", None)
             self.needs_grad[n] = self.external or (n.head and n.loss_weight != 0.0) or any(
-                self.needs_grad[c] for c in n.consumers) or (rc is not None and self.needs_grad[rc])
+                self.needs_grad[c] for c in n.consumers) or (
+                    rc is not None and self.needs_grad[rc]) or bool(n.mse_grad)
         # all gradients in ONE flat buffer (a single RCCL all-reduce under data parallelism)
         plist = [(n, p, key, m) for n in self.nodes for (p, key, m) in n.params()]
         self.gflat = _f32(sum(p.numel() for _, p, _, _ in plist), dev)
@@ -981,9 +1030,12 @@ class Engine:
         if self.loss_heads:
             if self.err_layer not in self.loss_heads:
                 raise NotImplementedError("err head without labels")
-            terms = self.loss_heads + self.reg_terms
-            for t in self.reg_terms:
+            terms = self.loss_heads + self.reg_terms + self.mse_terms
+            if len(terms) > 8:
+                raise NotImplementedError("more than 8 loss terms in loss_final")
+            for t in self.reg_terms + self.mse_terms:
                 t.row_loss = _f32(M, dev)
+            self.loss_terms = terms            # loss_out[2 + i]: the mean of term i (loss_term_mean)
             self.n_loss_terms = len(terms)
             self.loss_out = _f32(2 + len(terms), dev)
             self.loss_acc = _f32(2, dev)
@@ -991,6 +1043,9 @@ class Engine:
             self.loss_ptrs = torch.from_numpy(ptrs.view(np.int64)).to(dev)
             self.loss_w = torch.tensor([l.loss_weight for l in terms], dtype=torch.float32,
                                        device=dev)
+        elif self.mse_terms:
+            raise NotImplementedError("mse in a [model] without a labelled cost_nll head (the "
+                                      "loss reduction reports that head's error)")
         if self.seq:
             self.seq_meta = torch.zeros(4 * self.B, dtype=torch.int64, device=dev)
             # host side of the per-batch metadata upload: a ring of pinned slots, each reused only
@@ -1066,6 +1121,7 @@ class Engine:
                 # keeps no bf16 dz (its dW then runs in fp32 on the fp32 output), nor does a
                 # consumer that needs no gradient
                 n.f32_dead = (not keep_f32 and not n.ln
+                              and not any(t.node is n for t in self.mse_terms)
                               and all(c in mm and not c.ln and self.needs_grad[c]
                                       for c in n.consumers)
                               and not any(getattr(c, "qv0", 0) or getattr(c, "reads", 0)
@@ -1104,10 +1160,13 @@ class Engine:
         G = n.G
         n.lbuf = []
         K = n.K
+        # slabs in front of layer 0's dX slabs: the mse gradients of the node it reads
+        n.dx_res = len(n.src[1].mse_grad) if n.src[0] == "node" else 0
         for sp in n.layers:
             H = sp["H"]
             B2 = 2 * B if sp["bidir"] else B
             D = 2 * H if sp["bidir"] else H
+            xres = 0 if n.lbuf else n.dx_res
             lb = dict(K=K, H=H, B2=B2, D=D,
                       zslab=_f32(MAX_SPLITS * M * H, dev), wpre=_f32(G * M * H, dev),
                       xhat=_f32(G * M * H, dev), sm=_f32(G * H, dev), si=_f32(G * H, dev),
@@ -1119,7 +1178,7 @@ class Engine:
                       drop=_f32(B2 * H, dev), dgates=_f32(G * T * B2 * H, dev),
                       dpre=_f32(G * M * H, dev), dz=_f32(G * M * H, dev),
                       rwork=_f32(8 * B2 * H, dev), ut=_f32(G * H * H, dev),
-                      dx=_f32(G * MAX_SPLITS * M * K, dev),
+                      dx=_f32((G * MAX_SPLITS + xres) * M * K, dev),
                       dW=[None] * G, db=[None] * G, dU=[None] * G, dgamma=[None] * G,
                       dbeta=[None] * G, dgamma_ln=[None], dbeta_ln=[None])
             if sp.get("ln"):
@@ -2047,11 +2106,38 @@ class Engine:
             else:
                 self._fwd_epilogue(n, s, train)
             i += len(grp)
+        self._mse_kernels(s, train)
         if self.loss_heads and not defer_loss:
             self._k("loss_finalize", 0, 4.0 * self.M * (self.n_loss_terms + 1),
                     "pkc_loss_finalize", self.n_loss_terms, ptr(self.loss_ptrs), ptr(self.loss_w),
                     self.M, ptr(self.err_layer.row_err), ptr(self.loss_out), ptr(self.loss_acc),
                     None if self.seq else ptr(self.ctr), s)
+
+    def _mse_slabs(self, n):
+        """(buffer, slab stride) holding node n's mse gradient slabs, in front of its other
+        gradient slabs: a recurrent consumer's layer-0 dX buffer, or n's own gslab."""
+        rc = getattr(n, "rec_consumer", None)
+        return (rc.lbuf[0]["dx"] if rc is not None else n.gslab), self.M * n.N
+
+    def _mse_kernels(self, s, train):
+        """The mse terms' per-row losses and, in training, their gradients: slab k of the node's
+        gradient slabs for its k-th weighted term (the node's slab sum then folds it in).  The
+        target is a column range of the batch buffer; the weight is a head's, loss weight x
+        grad_scale.  Always the fp32 kernel on the node's fp32 output, whatever the matmuls run."""
+        M = self.M
+        for t in self.mse_terms:
+            n = t.node
+            dy = None
+            if train and t in n.mse_grad:
+                buf, st = self._mse_slabs(n)
+                dy = C.c_void_p(buf.data_ptr() + 4 * n.mse_grad.index(t) * st)
+                if getattr(n, "rec_consumer", None) is not None:
+                    # (a recurrent consumer that takes no gradient never rewrites this)
+                    n.gsrc = (buf, len(n.mse_grad), st)
+            self._k("mse_fused %s N=%d" % (t.name, n.N), 3.0 * M * n.N,
+                    4.0 * M * n.N * (3 if dy else 2), "pkc_mse_fused", M, n.N, ptr(n.out), n.N,
+                    C.c_void_p(self.x.data_ptr() + 4 * t.c0), self.F,
+                    C.c_float(t.loss_weight * self.grad_scale), dy, n.N, ptr(t.row_loss), s)
 
     def _conv_fwd(self, n, s, train):
         """A conv node's two forward launches: convolution + bias + max-pool, then norm /
@@ -2141,9 +2227,10 @@ class Engine:
         want = [1 if (c.W is None or self._wt(c.W, True) is not None)
                 else _splits(M, c.K, c.N, c.sxcap) for c in n.consumers]
         budget = SLAB_BUDGET_MULTI if len(n.consumers) > 1 and not self.cap else MAX_SPLITS
-        while sum(want) > budget and max(want) > 1:
+        budget -= len(n.mse_grad)          # the mse terms' slabs come first (_mse_kernels)
+        while want and sum(want) > budget and max(want) > 1:
             want[want.index(max(want))] -= 1
-        off = 0
+        off = len(n.mse_grad)
         n.cons_off = []
         for c, w in zip(n.consumers, want):
             c.sx = w
@@ -2284,6 +2371,7 @@ class Engine:
         without LayerNorm / SyncBN, a large batch, the 128x128 body for both operand forms."""
         if not (BN_BWD_EPI and self.M > 128 and not self.seq and P.bn and not P.ln and not P.head
                 and P.W is not None and len(P.consumers) == 1 and pr.splits == 1
+                and not P.mse_grad
                 and getattr(P, "bn_sums", None) is None and (P.drop == 0 or P.keep is not None)):
             return False
         lib = L.lib()
@@ -2367,7 +2455,7 @@ class Engine:
             sums = self._rec_wgrads(n, lb, dzs, x_ptr, ldx, hsrc, s, h16)
             # dX = sum_g dz_g W_g (one slab group per gate) in one grouped launch, with the weight
             # gradients' slab sums riding along
-            dxp, nx = [], 0
+            dxp, nx = [], (n.dx_res if li == 0 else 0)    # (after the source node's mse slabs)
             if li > 0 or want_dx0:
                 for g in range(n.G):
                     dz = dzs[g]
@@ -2969,6 +3057,13 @@ class Engine:
         v = self.loss_out.cpu()
         self._check_loops()
         return float(v[0]), float(v[1])
+
+    def loss_term_mean(self, name):
+        """The unweighted mean of the last step's mse term `name` (its [model] output name), as the
+        loss reduction stored it (forces a sync)."""
+        i = next(i for i, t in enumerate(self.loss_terms) if getattr(t, "name", None) == name
+                 and isinstance(t, MseTerm))
+        return float(self.loss_out[2 + i].item())
 
     def chunk_totals(self):
         """(loss_sum, err_sum) over the batches since bind_chunk (core.py:251-252)."""

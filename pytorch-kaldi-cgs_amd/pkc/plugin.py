@@ -30,6 +30,11 @@ gate's projection reads its own version, and the caller's tensor is rebound to t
 as with the reference.  Autograd does not see the rebinding (the reference's is through
 ``.data`` too): dL/dx is the plain dX of layer 0.
 
+The [model]'s costs stay the reference's here: cost_nll, and the mse of the joint
+speech-enhancement recipe (utils.py:2045-2048), are the reference's own torch expressions on the
+plug-ins' outputs, and autograd hands their gradients to ``backward`` — the external mode needs
+nothing for mse (the engine's own MseTerm / pkc_mse_fused path is pkc.core.run_nn's).
+
 Not supported here (raise NotImplementedError, run through pkc.core.run_nn instead): SyncBN.
 """
 import torch
