@@ -396,7 +396,14 @@ __device__ __forceinline__ void tile_colstats64(const f32x16& acc, Lds<PREC>& sm
   part[(int64_t)by * 2 * N + N + col] = red[2 * BN + cl] + red[3 * BN + cl];
 }
 
-template <int PREC, bool AKC, bool BKC, bool VEC, int DEPTH, bool BIN, bool STATS = false>
+// WIDE: the finished fp32 tile is staged through the workgroup's LDS (free after the k-loop) in two
+// 32-row halves and stored as 16-byte row pieces — four write-through (sc1) stores per lane instead
+// of sixteen 4-byte stores from the MFMA layout — when ldc and the tile's base are 16-byte
+// multiples and the tile is interior in N; other tiles keep the 4-byte form.  For outputs that a
+// later launch reads on other XCDs (the B = 128 step's dW); split-K slabs, which their consumers
+// read from the producer's own L2, keep the plain form (and with it their instruction stream).
+template <int PREC, bool AKC, bool BKC, bool VEC, int DEPTH, bool BIN, bool STATS = false,
+          bool WIDE = false>
 __device__ __forceinline__ void gemm_body(Lds<PREC>& sm, int bx, int by, int bz, int M, int N, int K,
                                           const void* __restrict__ Av, int64_t lda,
                                           const void* __restrict__ Bv, int64_t ldb,
@@ -498,7 +505,39 @@ __device__ __forceinline__ void gemm_body(Lds<PREC>& sm, int bx, int by, int bz,
   // C/D map of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
   const int col = n0 + wn * 32 + r;
   const int row0 = m0 + wm * 32 + 4 * h;
-  if (col < N) {
+  bool wide = false;
+  if constexpr (WIDE) {
+    float* Ct = C + (int64_t)bz * slab_stride + (int64_t)m0 * ldc + n0;
+    // uniform; ldc <= 2^23 keeps a half-tile's byte offsets below 2^31
+    wide = ldc % 4 == 0 && ldc <= (1 << 23) && (uintptr_t)Ct % 16 == 0 && n0 + BN <= N;
+    if (wide) {
+      constexpr int SLD = BN + 4;                     // 272-byte rows: 32 of them fit every Lds
+      static_assert(32 * SLD * sizeof(float) <= sizeof(Lds<PREC>), "staging half-tile exceeds LDS");
+      float* st = reinterpret_cast<float*>(&sm);
+      const int ldci = (int)ldc;
+      const int sr = threadIdx.x >> 4, sc = (threadIdx.x & 15) * 4;
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        __syncthreads();          // the last fragment reads / the previous half's reads are done
+        if (wm == half) {
+#pragma unroll
+          for (int reg = 0; reg < 16; ++reg)
+            st[((reg & 3) + 8 * (reg >> 2) + 4 * h) * SLD + wn * 32 + r] = acc[reg];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int rl = half * 32 + sr + 16 * i;
+          if (m0 + rl < M) {
+            const float4 v = *reinterpret_cast<const float4*>(&st[(sr + 16 * i) * SLD + sc]);
+            st16_wt(Ct + (int64_t)half * 32 * ldc, ((sr + 16 * i) * ldci + sc) * 4, v);
+          }
+        }
+      }
+      if constexpr (STATS) __syncthreads();
+    }
+  }
+  if (!wide && col < N) {
     float* Cr = C + (int64_t)bz * slab_stride + (int64_t)row0 * ldc + col;
     const int ldci = (int)ldc;          // < 2^26 (pkc_gemm checks): dr * ldci fits 32 bits
 #pragma unroll
@@ -774,14 +813,15 @@ __device__ __forceinline__ void grouped_body(const GroupArgs& g) {
 #undef PKC_GS
     return;
   }
-#define PKC_GB(AK, BK_, V)                                                                      \
-  gemm_body<PREC, AK, BK_, V, GD, BIN>(sm, bx, by, bz, p.M, p.N, p.K, p.A, p.lda, p.B, p.ldb, p.C, \
-                                      p.ldc, p.kchunk, p.slab)
+#define PKC_GB(AK, BK_, V) PKC_GBE(AK, BK_, V, false)
+#define PKC_GBE(AK, BK_, V, E)                                                                  \
+  gemm_body<PREC, AK, BK_, V, GD, BIN, false, E>(sm, bx, by, bz, p.M, p.N, p.K, p.A, p.lda, p.B,  \
+                                                 p.ldb, p.C, p.ldc, p.kchunk, p.slab)
   if constexpr (VO) {
     switch (p.code) {
       case 7: PKC_GB(true, true, true); break;
       case 5: PKC_GB(true, false, true); break;
-      case 1: PKC_GB(false, false, true); break;
+      case 1: PKC_GBE(false, false, true, true); break;     // dW: wide write-through epilogue
       default: PKC_GB(false, true, true); break;
     }
     return;
@@ -797,6 +837,7 @@ __device__ __forceinline__ void grouped_body(const GroupArgs& g) {
     default: PKC_GB(false, true, false); break;
   }
 #undef PKC_GB
+#undef PKC_GBE
 }
 
 template <int PREC, bool BIN, bool BIG, bool SP = false, bool SUM = false>

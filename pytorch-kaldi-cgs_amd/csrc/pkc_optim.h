@@ -24,11 +24,15 @@ __device__ __forceinline__ void opt_update(const pkc_opt_tensor& t, OptState& e)
     p = p + (-t.lr) * g;
   } else if (t.kind == PKC_OPT_RMSPROP) {
     // torch/optim/rmsprop.py: sq = alpha*sq + (1-alpha)*g^2; avg = sqrt(sq) + eps
-    const float sq = e.s1 * t.alpha + (1.f - t.alpha) * g * g;
+    // The two-product sums are spelled as ONE fused form (the one the 16-byte path compiled to).
+    // Left to the compiler they were fused differently per path — fma(g, (1 - alpha) g, s1 alpha)
+    // in the vector path, two packed multiplies and an add in the scalar path — so a tensor's
+    // result depended on its pointers' alignment by one unit in the last place.
+    const float sq = __builtin_fmaf(g, (1.f - t.alpha) * g, e.s1 * t.alpha);
     e.s1 = sq;
     float avg;
     if (t.centered) {
-      const float ga = e.s2 * t.alpha + (1.f - t.alpha) * g;
+      const float ga = __builtin_fmaf(t.alpha, e.s2, (1.f - t.alpha) * g);
       e.s2 = ga;
       avg = sqrtf(sq - ga * ga) + t.eps;
     } else {
@@ -81,9 +85,22 @@ __device__ __forceinline__ float quant_w(float p, int bits) {
 #endif
 constexpr int OPT_T = 256, OPT_PER = PKC_OPT_PER, OPT_CHUNK = OPT_T * OPT_PER;
 
+// 16 bytes to base + off bytes as a write-through (sc1) store: for streams that nothing in the
+// launch reads again and whose next reader is a later launch on any XCD, so the line leaves the
+// producing XCD's L2 as it is written instead of at the end of the launch.  base is uniform over
+// the wave (it goes into a buffer descriptor, which lives in scalar registers), off < 2^31.
+__device__ __forceinline__ void st16_wt(void* base, unsigned off, float4 v) {
+  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+  __builtin_amdgcn_raw_buffer_store_b128(
+      __builtin_bit_cast(u32x4, v),
+      __builtin_amdgcn_make_buffer_rsrc(base, (short)0, 0x7fffffff, 0x00020000), (int)off, 0,
+      16);                                                                        // aux 16: sc1
+}
+
 // Every operand of a thread's OPT_PER elements is requested before any is used (independent
 // loads in flight instead of one round trip per element); states the optimizer does not keep are
-// never touched.  VEC: the tensor's pointers are 16-byte aligned and n % 4 == 0.
+// never touched.  VEC: the tensor's pointers are 16-byte aligned and n % 4 == 0; what it writes
+// (p, the states, the quantised and bf16 copies) goes out as 16-byte write-through stores.
 // DIRECT: the streams to touch follow from the pointers alone (pkc_opt_seg: s1 NULL when the update
 // keeps no first state, qout NULL unless quantised), so no load waits on the descriptor's fields.
 template <bool VEC, bool DIRECT = false>
@@ -106,8 +123,12 @@ __device__ __forceinline__ void optim_chunk(const pkc_opt_tensor& t, int64_t sta
       if (st3) S3[j] = *reinterpret_cast<const float4*>(t.s3 + i);
       if (msk) MK[j] = *reinterpret_cast<const float4*>(t.mask + i);
     }
+    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+    typedef __attribute__((ext_vector_type(2))) int i32x2;
+    i32x2 H[NV];                       // the vectors' bf16 roundings (8 bytes each)
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
+      H[j] = i32x2{0, 0};
       if (idx[j] >= t.n) break;
       float* pp = &P[j].x; float* gg = &G[j].x; float* a1 = &S1[j].x; float* a2 = &S2[j].x;
       float* a3 = &S3[j].x; float* mm = &MK[j].x;
@@ -121,17 +142,47 @@ __device__ __forceinline__ void optim_chunk(const pkc_opt_tensor& t, int64_t sta
         pp[l] = e.p; a1[l] = e.s1; a2[l] = e.s2; a3[l] = e.s3;
         if (qw) qq[l] = quant_w(e.p, t.qbits);
       }
-      const int64_t i = idx[j];
-      *reinterpret_cast<float4*>(t.p + i) = P[j];
-      if (st1) *reinterpret_cast<float4*>(t.s1 + i) = S1[j];
-      if (st2) *reinterpret_cast<float4*>(t.s2 + i) = S2[j];
-      if (st3) *reinterpret_cast<float4*>(t.s3 + i) = S3[j];
-      if (qw) *reinterpret_cast<float4*>(t.qout + i) = Q;
-      if (t.bout) {   // one 8-byte store (bout % 8 == 0 on this path)
-        typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-        bf16x4 h;
-        h[0] = (__bf16)P[j].x; h[1] = (__bf16)P[j].y; h[2] = (__bf16)P[j].z; h[3] = (__bf16)P[j].w;
-        *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(t.bout) + i) = h;
+      const unsigned off = (threadIdx.x + j * OPT_T) * V * 4;       // bytes from the item's start
+      st16_wt(t.p + start, off, P[j]);
+      if (st1) st16_wt(t.s1 + start, off, S1[j]);
+      if (st2) st16_wt(t.s2 + start, off, S2[j]);
+      if (st3) st16_wt(t.s3 + start, off, S3[j]);
+      if (qw) st16_wt(t.qout + start, off, Q);
+      bf16x4 h;
+      h[0] = (__bf16)P[j].x; h[1] = (__bf16)P[j].y; h[2] = (__bf16)P[j].z; h[3] = (__bf16)P[j].w;
+      H[j] = __builtin_bit_cast(i32x2, h);
+    }
+    if (t.bout) {
+      static_assert(NV == 2, "the bf16 copy pairs the two vectors of adjacent lanes");
+      __bf16* bo = reinterpret_cast<__bf16*>(t.bout);
+      if ((uintptr_t)t.bout % 16 == 0) {
+        // Lanes 2k and 2k + 1 hold adjacent 4-element groups of both vectors.  They swap one
+        // rounding each (the even lane gives its second, the odd lane its first), so that the even
+        // lane holds the 8 bf16 of the pair's first vectors and the odd lane those of the second:
+        // ONE 16-byte store per lane.  A pair whose odd half lies past n (n % 8 == 4) keeps the
+        // 8-byte store of the even lane's own group.
+        const bool odd = threadIdx.x & 1;
+        const i32x2 give = odd ? H[0] : H[1];
+        i32x2 got;                                    // quad_perm [1, 0, 3, 2]: lane ^ 1
+        got[0] = __builtin_amdgcn_mov_dpp(give[0], 0xB1, 0xF, 0xF, true);
+        got[1] = __builtin_amdgcn_mov_dpp(give[1], 0xB1, 0xF, 0xF, true);
+        typedef __attribute__((ext_vector_type(4))) int i32x4;
+        if (!odd) {
+          if (idx[0] + V < t.n) {
+            st16_wt(bo + start, threadIdx.x * V * 2,
+                                __builtin_bit_cast(float4, i32x4{H[0][0], H[0][1], got[0], got[1]}));
+          } else if (idx[0] < t.n) {
+            *reinterpret_cast<i32x2*>(bo + idx[0]) = H[0];
+          }
+          if (idx[1] < t.n && idx[1] + V >= t.n) *reinterpret_cast<i32x2*>(bo + idx[1]) = H[1];
+        } else if (idx[1] < t.n) {
+          st16_wt(bo + start, (threadIdx.x - 1 + OPT_T) * V * 2,
+                              __builtin_bit_cast(float4, i32x4{got[0], got[1], H[1][0], H[1][1]}));
+        }
+      } else {   // bout only 8-byte aligned: one 8-byte store per vector
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+          if (idx[j] < t.n) *reinterpret_cast<i32x2*>(bo + idx[j]) = H[j];
       }
     }
   } else {
