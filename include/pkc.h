@@ -24,7 +24,9 @@ extern "C" {
  * 4: PKC_PREC_BF16X3; 5: pkc_rnn_args.step_bf16 and its bf16 operand copies;
  * 6: pkc_bn_bwd_epi, pkc_gemm_bnbwd_ok, pkc_dense_bwd_pre;
  * 7: pkc_src_digest, pkc_gemm_grouped_tile, pkc_rnn_args.persist_* (persistent liGRU time loops);
- * 8: pkc_rnn_args.qh_exact (exact quantised-h step products). */
+ * 8: pkc_rnn_args.qh_exact (exact quantised-h step products).
+ * pkc_combine_args and its three entry points joined under 9 without a bump: no existing struct or
+ * entry point changed (tests/test_model_ops_cpu.py checks the new struct's layout). */
 #define PKC_ABI_VERSION 9
 
 enum { PKC_OK = 0, PKC_ERR_ARG = -1, PKC_ERR_HIP = -2, PKC_ERR_IO = -3, PKC_ERR_UNSUPPORTED = -4 };
@@ -253,6 +255,49 @@ int pkc_nll_fused(const pkc_nll_args* a, void* stream);
  * scalar otherwise (a target that is a column range of the batch buffer). */
 int pkc_mse_fused(int M, int N, const float* y, int64_t ldy, const float* target, int64_t ldt,
                   float weight, float* dy, int64_t lddy, float* row_loss, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The [model] tensor operations on produced outputs (utils.py:2014-2043): one elementwise launch
+ * forward, one backward, for a graph node that combines two row matrices (or one and a constant).
+ *   CONCAT      out = [a | b] along the columns (utils.py:2014-2016), N = Na + Nb
+ *   SUM         out = a + b                     (utils.py:2025-2026 on tensors)
+ *   MULT        out = a * b                     (utils.py:2020-2021)
+ *   AVG         out = (a + b) * 0.5f            (utils.py:2040-2041, / 2)
+ *   SUM_CONST   out = a + c                     (utils.py:2035-2036)
+ *   MULT_CONST  out = a * c                     (utils.py:2030-2031 on a tensor)
+ * a is (M x Na, lda), b (M x Nb, ldb); Na == Nb except for CONCAT; the constant forms read c and
+ * neither b nor Nb (0 or Na).  Either operand may be a column range of the batch buffer (ld = F,
+ * a pointer at any 4-byte offset).  fp32 arithmetic, one rounding per operation as written above,
+ * never contracted into an fma.
+ * forward: out (M x N, tight), and when out_bf16 is non-NULL the round-to-nearest-even bf16 copy
+ *   of the same values (the operand copy the bf16 matmuls read).
+ * backward: g = gslab[0] + gslab[1] + ... (nslab slabs of M x N, slab_stride floats apart, summed
+ *   left to right in fp32); da (M x Na, tight) and / or db (M x Nb, tight), either NULL for an
+ *   operand that takes no gradient (not both; the constant forms take da only):
+ *   CONCAT the two column ranges of g; SUM / SUM_CONST g; AVG g * 0.5f; MULT da = g * b,
+ *   db = g * a (the only form that reads a / b); MULT_CONST g * c.
+ * No atomics and no cross-thread sums: reruns are bit-identical.  16-byte loads and stores when
+ * every pointer, leading dimension, slab stride and width (for CONCAT Na too) allows them, the
+ * scalar form with identical results otherwise.
+ * Refused (PKC_ERR_ARG): unequal widths outside CONCAT, M or a width <= 0, a leading dimension
+ * below its width, nslab < 1, both da and db NULL.
+ * ------------------------------------------------------------------------------------------- */
+enum { PKC_COMBINE_CONCAT = 0, PKC_COMBINE_SUM = 1, PKC_COMBINE_MULT = 2, PKC_COMBINE_AVG = 3,
+       PKC_COMBINE_SUM_CONST = 4, PKC_COMBINE_MULT_CONST = 5 };
+typedef struct {
+  int op, M, Na, Nb;
+  const float* a; int64_t lda;
+  const float* b; int64_t ldb;
+  float c;
+  float* out; void* out_bf16;                              /* forward */
+  int nslab; const float* gslab; int64_t slab_stride;      /* backward */
+  float* da; float* db;
+} pkc_combine_args;
+/* 1 when the forward (backward != 0: the backward) takes these arguments, else 0 with the reason
+ * in pkc_last_error() */
+int pkc_combine_ok(const pkc_combine_args* a, int backward);
+int pkc_combine_fwd(const pkc_combine_args* a, void* stream);
+int pkc_combine_bwd(const pkc_combine_args* a, void* stream);
 
 /* LogSoftmax backward for an upstream gradient dy (M x N, row-major): dz = dy - exp(logp) *
  * rowsum(dy).  The architecture plug-in's trainable head forward (neural_networks.py:73-74 under

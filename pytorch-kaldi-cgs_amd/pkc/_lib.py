@@ -130,7 +130,21 @@ class RegItem(C.Structure):
                 ("c0", C.c_int), ("c1", C.c_int), ("block", C.c_int), ("assign", C.c_int)]
 
 
+# include/pkc.h PKC_COMBINE_*: the [model] tensor operations of a combining node
+COMBINE = {"concatenate": 0, "sum": 1, "mult": 2, "avg": 3, "sum_constant": 4, "mult_constant": 5}
+
+
+class CombineArgs(C.Structure):
+    _fields_ = [("op", C.c_int), ("M", C.c_int), ("Na", C.c_int), ("Nb", C.c_int),
+                ("a", vp), ("lda", i64), ("b", vp), ("ldb", i64), ("c", C.c_float),
+                ("out", vp), ("out_bf16", vp), ("nslab", C.c_int), ("gslab", vp),
+                ("slab_stride", i64), ("da", vp), ("db", vp)]
+
+
 _SIGS = {
+    "pkc_combine_ok": (C.c_int, [C.POINTER(CombineArgs), C.c_int]),
+    "pkc_combine_fwd": (C.c_int, [C.POINTER(CombineArgs), vp]),
+    "pkc_combine_bwd": (C.c_int, [C.POINTER(CombineArgs), vp]),
     "pkc_conv1d_ok": (C.c_int, [C.POINTER(Conv1dArgs)]),
     "pkc_conv1d_fwd": (C.c_int, [C.POINTER(Conv1dArgs), vp]),
     "pkc_conv1d_bwd_work_size": (i64, [C.POINTER(Conv1dArgs)]),

@@ -156,6 +156,8 @@ def model_init(config, arch_dict, fea_dims, to_do):
     for out, op, a, b in parse_model(config["model"]["model"]):
         if op == "concatenate":                          # utils.py:1805-1809
             out_dims[out] = out_dims[a] + out_dims[b]
+        if op in ("mult", "sum", "mult_constant", "sum_constant", "avg") and a in out_dims:
+            out_dims[out] = out_dims[a]                  # utils.py:1827-1828 (tensor operands)
         if op != "compute":
             continue
         sec = arch_dict[a][0]
