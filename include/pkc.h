@@ -26,7 +26,8 @@ extern "C" {
  * 7: pkc_src_digest, pkc_gemm_grouped_tile, pkc_rnn_args.persist_* (persistent liGRU time loops);
  * 8: pkc_rnn_args.qh_exact (exact quantised-h step products).
  * pkc_combine_args and its three entry points joined under 9 without a bump: no existing struct or
- * entry point changed (tests/test_model_ops_cpu.py checks the new struct's layout). */
+ * entry point changed (tests/test_model_ops_cpu.py checks the new struct's layout).  pkc_rnn_std_args
+ * and pkc_rnn_std_fwd / _bwd joined the same way (tests/test_cudnn_cpu.py checks its layout). */
 #define PKC_ABI_VERSION 9
 
 enum { PKC_OK = 0, PKC_ERR_ARG = -1, PKC_ERR_HIP = -2, PKC_ERR_IO = -3, PKC_ERR_UNSUPPORTED = -4 };
@@ -572,6 +573,55 @@ int pkc_rnn_persist_geometry(int* nwaves, int* nslots_fwd, int* nslots_bwd, int*
 int pkc_rnn_persist_form(const pkc_rnn_args* a, int bwd);
 int pkc_rnn_fwd(const pkc_rnn_args* a, void* stream);
 int pkc_rnn_bwd(const pkc_rnn_args* a, float* dpre, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Standard-cell recurrent layers: the time loops of LSTM_cudnn, GRU_cudnn and RNN_cudnn
+ * (neural_networks.py:364-465: torch.nn.LSTM / GRU / RNN).  Additive to ABI 9: a new struct and new
+ * entry points only.  One layer, both directions; direction d (1: reverse, walks time T-1 .. 0) has
+ * its own operands and is a grid dimension of every step launch.
+ *   wpre[d] (T, B, G*H), rows in natural time: the packed input projection weight_ih x + bias_ih;
+ *   U[d]    (G*H, H): weight_hh as torch packs it, gate rows i,f,g,o (LSTM), r,z,n (GRU);
+ *   bhh[d]  (G*H): bias_hh, or NULL (bias = False).  The step adds it to the recurrent product.
+ * Cells (a = wpre, u = U h_{t-1} + bhh):
+ *   LSTM  i,f,o = sig(a + u), g = tanh(a_g + u_g), c = f c_{t-1} + i g, h = o tanh(c)
+ *   GRU   r,z = sig(a + u), n = tanh(a_n + r u_n), h = (1 - z) n + z h_{t-1}
+ *         (torch's cell: the reset gate multiplies AFTER the recurrent product, and b_hn is inside
+ *         it — so b_hn can not be folded into the projection: its gradient is sum r da_n)
+ *   RNN   h = act(a + u), act = PKC_ACT_TANH or PKC_ACT_RELU
+ * Forward: one launch per time step.  Saves hs (ndir, T+1, B, H) — direction 0 keeps the state
+ * after time t in slot t+1 (slot 0 = the zero initial state), direction 1 in slot t (slot T = 0), so
+ * that h_{t-1} of the T steps are T consecutive slots in natural time —, cs (LSTM, same layout),
+ * the gate activations gates (ndir, T, B, G*H), un (GRU: u_n, (ndir, T, B, H)) and writes the layer
+ * output y (T, B, ndir*H).  Inter-layer dropout (train != 0 and drop_p > 0; the caller passes
+ * drop_p = 0 for the last layer): y = h keep / (1 - p) with keep ~ Bernoulli(1 - p) per element of
+ * y, drawn from the counter-hash stream of pkc_dense_fwd (index = the element's flat index in y) or
+ * read from keep_in; keep (u8, the layout of y) is written for the backward.  hs stays undropped.
+ * Backward (pkc_rnn_std_bwd): dy = dL/dy as dy_nslab partial slabs; writes dgates
+ * (ndir, T, B, GD*H), rows in natural time, the gradients of the pre-activations: GD = G slabs in
+ * gate order, except the GRU's GD = 4 slabs [r, z, n_rec, n_in] with n_in = da_n (input side: dW_in,
+ * db_in, dx) and n_rec = r da_n (recurrent side: dU_n, db_hn).  So per direction
+ *   d weight_ih = dA^T x, d bias_ih = colsum dA, dx += dA weight_ih    (dA: the G input-side slabs)
+ *   d weight_hh = dR^T h_{t-1}, d bias_hh = colsum dR                  (dR: the G recurrent-side slabs;
+ *   LSTM / RNN: dR = dA), all plain matmuls over the T*B rows.  ut: (ndir, H, G*H) floats of scratch
+ *   (the transposed weight_hh), work: (ndir, 2, B, H) floats (carries).
+ * No atomics: reruns are bit-identical, and a bidirectional call equals two one-direction calls.
+ * H <= 2048; PKC_ERR_ARG with a pkc_last_error() text for a null pointer or a bad shape.
+ * ------------------------------------------------------------------------------------------- */
+enum { PKC_STD_LSTM = 0, PKC_STD_GRU = 1, PKC_STD_RNN = 2 };
+typedef struct {
+  int cell, T, B, H, ndir, act, train;
+  const float* wpre[2];
+  const float* U[2];
+  const float* bhh[2];
+  float* hs; float* cs; float* gates; float* un; float* y;
+  float drop_p; uint64_t seed; const int64_t* step_ctr; int64_t stream_id;
+  const uint8_t* keep_in;      /* optional injected keep mask (T, B, ndir*H) */
+  uint8_t* keep;               /* (T, B, ndir*H) mask in use */
+  const float* dy; int dy_nslab; int64_t dy_slab_stride;
+  float* dgates; float* ut; float* work;
+} pkc_rnn_std_args;
+int pkc_rnn_std_fwd(const pkc_rnn_std_args* a, void* stream);
+int pkc_rnn_std_bwd(const pkc_rnn_std_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Host-side Kaldi ark I/O (data_io.py:770-806 write_mat; 645-711 read_mat_ark binary FM/DM).

@@ -141,7 +141,24 @@ class CombineArgs(C.Structure):
                 ("slab_stride", i64), ("da", vp), ("db", vp)]
 
 
+# include/pkc.h PKC_STD_*: the cells of the *_cudnn architectures (torch.nn.LSTM / GRU / RNN)
+STD_LSTM, STD_GRU, STD_RNN = 0, 1, 2
+
+
+class RnnStdArgs(C.Structure):
+    _fields_ = [("cell", C.c_int), ("T", C.c_int), ("B", C.c_int), ("H", C.c_int),
+                ("ndir", C.c_int), ("act", C.c_int), ("train", C.c_int),
+                ("wpre", vp * 2), ("U", vp * 2), ("bhh", vp * 2),
+                ("hs", vp), ("cs", vp), ("gates", vp), ("un", vp), ("y", vp),
+                ("drop_p", C.c_float), ("seed", C.c_uint64), ("step_ctr", vp), ("stream_id", i64),
+                ("keep_in", vp), ("keep", vp),
+                ("dy", vp), ("dy_nslab", C.c_int), ("dy_slab_stride", i64),
+                ("dgates", vp), ("ut", vp), ("work", vp)]
+
+
 _SIGS = {
+    "pkc_rnn_std_fwd": (C.c_int, [C.POINTER(RnnStdArgs), vp]),
+    "pkc_rnn_std_bwd": (C.c_int, [C.POINTER(RnnStdArgs), vp]),
     "pkc_combine_ok": (C.c_int, [C.POINTER(CombineArgs), C.c_int]),
     "pkc_combine_fwd": (C.c_int, [C.POINTER(CombineArgs), vp]),
     "pkc_combine_bwd": (C.c_int, [C.POINTER(CombineArgs), vp]),

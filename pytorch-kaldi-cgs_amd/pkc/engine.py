@@ -595,6 +595,52 @@ class RecNode:
         return q[0] if q is not None else p
 
 
+class StdRecNode(RecNode):
+    """A whole LSTM_cudnn / GRU_cudnn / RNN_cudnn architecture (torch.nn.LSTM / GRU / RNN) as one
+    graph node: per layer and direction a packed weight_ih (G*H, K), weight_hh (G*H, H) and the two
+    biases, the standard-cell time loops of pkc_rnn_std_fwd / _bwd, dropout between layers.
+    layer_specs() contract: dict(std, H, act, bidir, ndir, drop (of the layer's output; 0 on the
+    last), W / U / bih / bhh: one entry per direction (biases None without bias))."""
+    std = True
+
+    def __init__(self, arch, net, K):
+        self.arch, self.net, self.K = arch, net, K
+        self.name = arch
+        self.std_cell = net.std_cell
+        self.cell = None                 # none of the pkc_rnn_args cells
+        self.cid = {"lstm": L.STD_LSTM, "gru": L.STD_GRU, "rnn": L.STD_RNN}[net.std_cell]
+        self.G = net.STD_GATES
+        # gate-gradient slabs per row: the GRU keeps r * da_n (recurrent side) beside da_n
+        self.GD = 4 if net.std_cell == "gru" else self.G
+        self.cand = None
+        self.layers = net.layer_specs()
+        self.N = net.out_dim
+        self.src = None
+        self.consumers = []
+        self.loss_weight = 0.0
+        self.label_col = None
+        for sp in self.layers:
+            if sp["act"] not in ("tanh", "relu"):
+                raise NotImplementedError("%s: nonlinearity %s (tanh or relu)" % (arch, sp["act"]))
+            if not 0.0 <= sp["drop"] < 1.0:
+                raise ValueError("%s: dropout %s outside [0, 1)" % (arch, sp["drop"]))
+        self.ibits = 0
+        self.reads = 0
+        self.qw = {}
+        self.emask = {}
+
+    def params(self):
+        out = []
+        for li, sp in enumerate(self.layers):
+            for d in range(sp["ndir"]):
+                out.append((sp["W"][d], ("dW", li, d), None))
+                out.append((sp["U"][d], ("dU", li, d), None))
+                if sp["bih"][d] is not None:
+                    out.append((sp["bih"][d], ("dbih", li, d), None))
+                    out.append((sp["bhh"][d], ("dbhh", li, d), None))
+        return out
+
+
 def pattern_effective_masks(net, s):
     """Pattern masks (neural_networks.py:263-272, 876-884; sparsity.py:1112-1146) of one
     architecture: computed once, at the first layer call, from |W| of every pattern-masked weight —
@@ -791,7 +837,7 @@ class Engine:
                         src[1].consumers.append(nl)
                     self.nodes.append(nl)
                     src = ("node", nl)
-                node = RecNode(a, net, K)
+                node = (StdRecNode if hasattr(net, "std_cell") else RecNode)(a, net, K)
                 node.src = src
                 if src[0] == "node":
                     if getattr(src[1], "rec_consumer", None) is not None:
@@ -896,6 +942,12 @@ class Engine:
                     scal[out] = {}
                     continue
                 if op == "cost_gl":
+                    std = [arch for arch, net in self.nets.items() if hasattr(net, "std_cell")
+                           and not getattr(net, "skip_regularization", False)]
+                    if std:
+                        raise NotImplementedError("cost_gl over the %s architecture %s (packed "
+                                                  "per-direction weights) is not on the pkc path"
+                                                  % (type(self.nets[std[0]]).__name__, std[0]))
                     if any(q.dim() > 2 for q in params) or any(
                             hasattr(net, "conv_specs") for net in self.nets.values()
                             if not getattr(net, "skip_regularization", False)):
@@ -1274,7 +1326,40 @@ class Engine:
             if getattr(n, "W_h", None) is not None:
                 call("pkc_cast_bf16", ptr(n.W), ptr(n.W_h), n.W.numel(), s)
 
+    def _alloc_std(self, n):
+        """Buffers of a StdRecNode (layouts: include/pkc.h, pkc_rnn_std_args)."""
+        M, dev, B, T = self.Mmax, self.dev, self.B, self.max_len
+        G, GD = n.G, n.GD
+        n.lbuf = []
+        K = n.K
+        n.dx_res = len(n.src[1].mse_grad) if n.src[0] == "node" else 0
+        for sp in n.layers:
+            H, nd = sp["H"], sp["ndir"]
+            D = nd * H
+            xres = 0 if n.lbuf else n.dx_res
+            nx = nd * (2 if n.std_cell == "gru" else 1) * MAX_SPLITS      # dX slab groups
+            lb = dict(K=K, H=H, B2=nd * B, D=D, nd=nd,
+                      zslab=_f32(MAX_SPLITS * M * G * H, dev), wpre=_f32(nd * M * G * H, dev),
+                      work=_f32(L.lib().pkc_dense_work_size(M, G * H), dev),
+                      hs=_f32(nd * (T + 1) * B * H, dev),
+                      cs=_f32(nd * (T + 1) * B * H, dev) if n.std_cell == "lstm" else None,
+                      un=_f32(nd * M * H, dev) if n.std_cell == "gru" else None,
+                      gates=_f32(nd * M * G * H, dev), y=_f32(M * D, dev),
+                      keep=(torch.zeros(M * D, dtype=torch.uint8, device=dev)
+                            if sp["drop"] > 0 else None),
+                      dgates=_f32(nd * M * GD * H, dev), ut=_f32(nd * H * G * H, dev),
+                      rwork=_f32(nd * 2 * B * H, dev), dbt=_f32(nd * GD * H, dev),
+                      dx=_f32((nx + xres) * M * K, dev),
+                      dW=[None] * nd, dU=[None] * nd, dbih=[None] * nd, dbhh=[None] * nd)
+            n.lbuf.append(lb)
+            K = D
+        n.rslab = None
+        n.dysum = _f32(M * max(lb["D"] for lb in n.lbuf), dev) if REC_DY_PRESUM else None
+        n.out = n.lbuf[-1]["y"]
+
     def _alloc_rec(self, n):
+        if getattr(n, "std", False):
+            return self._alloc_std(n)
         M, dev, B, T = self.Mmax, self.dev, self.B, self.max_len
         G = n.G
         n.lbuf = []
@@ -2092,6 +2177,10 @@ class Engine:
         for n in self.nodes:
             if not n.rec:
                 continue
+            if getattr(n, "std", False):      # standard cells: one exact-fp32 launch per step
+                for li in range(len(n.layers)):
+                    out["%s.%d" % (n.arch, li)] = "fp32 steps"
+                continue
             for li in range(len(n.layers)):
                 a = self._rnn_args(n, li, True, self.max_len)
                 lb = n.lbuf[li]
@@ -2124,7 +2213,150 @@ class Engine:
         vs = [(lb["xq"].data_ptr() + 4 * g * M * K, K) for g in range(G)]
         return vs, vs[-1]
 
+    def _std_args(self, n, li, train, T):
+        sp, lb = n.layers[li], n.lbuf[li]
+        H, nd, M = lb["H"], lb["nd"], T * self.B
+        a = L.RnnStdArgs()
+        a.cell, a.T, a.B, a.H, a.ndir = n.cid, T, self.B, H, nd
+        a.act, a.train = L.ACT[sp["act"]], int(train)
+        for d in range(nd):
+            a.wpre[d] = lb["wpre"].data_ptr() + 4 * d * M * n.G * H
+            a.U[d] = sp["U"][d].data_ptr()
+            a.bhh[d] = sp["bhh"][d].data_ptr() if sp["bhh"][d] is not None else None
+        a.hs = lb["hs"].data_ptr()
+        a.cs = lb["cs"].data_ptr() if lb["cs"] is not None else None
+        a.un = lb["un"].data_ptr() if lb["un"] is not None else None
+        a.gates, a.y = lb["gates"].data_ptr(), lb["y"].data_ptr()
+        a.drop_p = float(sp["drop"])
+        a.seed = self.seed
+        a.step_ctr = self.ctr.data_ptr()
+        a.stream_id = zlib.crc32(("%s.%d" % (n.arch, li)).encode())
+        din = self.rnn_drop_in.get((n.arch, li))
+        a.keep_in = din.data_ptr() if din is not None else None
+        a.keep = lb["keep"].data_ptr() if lb["keep"] is not None else None
+        a.dgates, a.ut, a.work = lb["dgates"].data_ptr(), lb["ut"].data_ptr(), lb["rwork"].data_ptr()
+        return a
+
+    def _std_input(self, n, li):
+        """(pointer, ld) of layer li's input rows."""
+        if li == 0:
+            return self._src(n)
+        prev = n.lbuf[li - 1]
+        return prev["y"].data_ptr(), prev["D"]
+
+    def _std_fwd(self, n, s, train):
+        """Forward of a StdRecNode: per layer and direction ONE packed projection matmul
+        (all gates) with bias_ih in its epilogue, then the time loop of both directions."""
+        M, T = self.M, self.T
+        for li, (sp, lb) in enumerate(zip(n.layers, n.lbuf)):
+            H, K, GH = lb["H"], lb["K"], n.G * lb["H"]
+            x_ptr, ldx = self._std_input(n, li)
+            for d in range(lb["nd"]):
+                sf = _splits(M, GH, K, MAX_SPLITS)
+                self._k("rnn_std_gemm_W %dx%dx%d" % (M, GH, K), 2.0 * M * GH * K,
+                        4.0 * (M * K + GH * K + sf * M * GH), "pkc_gemm", self.prec, 1, 1, M, GH, K,
+                        C.c_void_p(x_ptr), ldx, ptr(sp["W"][d]), K, ptr(lb["zslab"]), GH, sf,
+                        M * GH, s)
+                a = L.DenseFwdArgs(
+                    M=M, N=GH, nslab=sf, zslab=lb["zslab"].data_ptr(), slab_stride=M * GH,
+                    bias=sp["bih"][d].data_ptr() if sp["bih"][d] is not None else None,
+                    norm=L.NORM_NONE, act=L.ACT["linear"], drop_p=0.0, seed=0, step_ctr=None,
+                    stream_id=0, keep_in=None, keep_out=None, xhat=None,
+                    out=lb["wpre"].data_ptr() + 4 * d * M * GH, momentum=0.05, eps=1e-5)
+                self._k("rnn_std_bias H=%d" % H, 0, 4.0 * M * GH * (sf + 1), "pkc_dense_fwd",
+                        C.byref(a), ptr(lb["work"]), s)
+            ra = self._std_args(n, li, train, T)
+            self._k("rnn_std_fwd_loop T=%d H=%d" % (T, H), 2.0 * T * lb["B2"] * GH * H,
+                    4.0 * T * lb["nd"] * GH * H, "pkc_rnn_std_fwd", C.byref(ra), s)
+
+    def _std_bwd(self, n, s, want_dx0=False, on_layer=None):
+        """BPTT of a StdRecNode, top layer first.  Per layer: the time loop (gate gradients of both
+        directions), then ONE grouped launch with every direction's d weight_ih = dA^T x,
+        d weight_hh = dR^T h_{t-1} and the bias column sums, then the dX = dA weight_ih slabs (the
+        next layer's dL/dy; its dropout is applied where that layer's loop reads them)."""
+        M, T, B = self.M, self.T, self.B
+        gs = getattr(n, "gsrc", None)
+        if gs is not None:
+            dy_t, dy_ns, dy_stride = gs[0], gs[1], gs[2]
+        else:
+            dy_t, dy_ns = n.gslab, n.sb
+            dy_stride = M * n.N
+        dy_ptr = dy_t.data_ptr()
+        G, GD, gru = n.G, n.GD, n.std_cell == "gru"
+        for li in reversed(range(len(n.layers))):
+            sp, lb = n.layers[li], n.lbuf[li]
+            H, K, nd = lb["H"], lb["K"], lb["nd"]
+            GH, GDH = G * H, GD * H
+            ra = self._std_args(n, li, True, T)
+            if dy_ns > 1 and n.dysum is not None:
+                self._rec_slab_sum_ptr(dy_ptr, dy_ns, M * lb["D"], dy_stride, n.dysum, s)
+                dy_ptr, dy_ns, dy_stride = n.dysum.data_ptr(), 1, M * lb["D"]
+            ra.dy, ra.dy_nslab, ra.dy_slab_stride = dy_ptr, dy_ns, dy_stride
+            self._k("rnn_std_bwd_loop T=%d H=%d" % (T, H), 2.0 * T * lb["B2"] * GH * H,
+                    4.0 * T * nd * GH * H, "pkc_rnn_std_bwd", C.byref(ra), s)
+            x_ptr, ldx = self._std_input(n, li)
+            wg, tail, dxp = [], [], []
+            nx = n.dx_res if li == 0 else 0
+            want_dx = li > 0 or want_dx0
+            for d in range(nd):
+                dg = lb["dgates"].data_ptr() + 4 * d * M * GDH
+                hp = lb["hs"].data_ptr() + 4 * (d * (T + 1) + d) * B * H     # h_{t-1}, natural time
+                dW, dU = lb["dW"][d].data_ptr(), lb["dU"][d].data_ptr()
+                # input-side column ranges of the gate-gradient rows -> weight_ih row ranges
+                # (GRU rows [r, z, n_rec, n_in]: r, z and n_in; else all G gates)
+                cols = [(0, 2 * H, 0), (3 * H, H, 2 * H)] if gru else [(0, GH, 0)]
+                for c0, w, r0 in cols:
+                    wg.append(("dWih%d %dx%dx%d" % (d, w, K, M), 2.0 * w * K * M,
+                               4.0 * (M * w + M * K + w * K),
+                               L.GemmProblem(a_kcontig=0, b_kcontig=0, M=w, N=K, K=M, splits=1,
+                                             A=dg + 4 * c0, lda=GDH, B=x_ptr, ldb=ldx,
+                                             C=dW + 4 * r0 * K, ldc=K, slab_stride=0)))
+                    if want_dx:
+                        sx = _splits(M, K, w, MAX_SPLITS)
+                        dxp.append(("dX%d %dx%dx%d" % (d, M, K, w), 2.0 * M * K * w,
+                                    4.0 * (M * w + w * K + sx * M * K),
+                                    L.GemmProblem(a_kcontig=1, b_kcontig=0, M=M, N=K, K=w, splits=sx,
+                                                  A=dg + 4 * c0, lda=GDH,
+                                                  B=sp["W"][d].data_ptr() + 4 * r0 * K, ldb=K,
+                                                  C=lb["dx"].data_ptr() + 4 * nx * M * K, ldc=K,
+                                                  slab_stride=M * K)))
+                        nx += sx
+                wg.append(("dWhh%d %dx%dx%d" % (d, GH, H, M), 2.0 * GH * H * M,
+                           4.0 * (M * GH + M * H + GH * H),
+                           L.GemmProblem(a_kcontig=0, b_kcontig=0, M=GH, N=H, K=M, splits=1, A=dg,
+                                         lda=GDH, B=hp, ldb=H, C=dU, ldc=H, slab_stride=0)))
+                if lb["dbih"][d] is not None:
+                    # column sums of the whole gate-gradient rows, then the two biases' ranges
+                    # (bias_hh: the recurrent side — for the GRU's b_hn, sum r da_n)
+                    bt = lb["dbt"].data_ptr() + 4 * d * GDH
+                    bi, bh = lb["dbih"][d].data_ptr(), lb["dbhh"][d].data_ptr()
+                    wg.append(("db%d colsum %dx%d" % (d, M, GDH), 0.0, 4.0 * M * GDH,
+                               L.GemmProblem(kind=L.OP_COLSUM, M=M, N=GDH, A=dg, C=bt)))
+
+                    def cp(src, dst, cnt, lab):
+                        return ("db%d copy %s" % (d, lab), 0.0, 8.0 * cnt,
+                                L.GemmProblem(kind=L.OP_SLABSUM, M=1, N=cnt, A=src, C=dst,
+                                              slab_stride=cnt))
+                    tail.append(cp(bt, bh, GH, "hh"))
+                    if gru:
+                        tail += [cp(bt, bi, 2 * H, "ih rz"), cp(bt + 12 * H, bi + 8 * H, H, "ih n")]
+                    else:
+                        tail.append(cp(bt, bi, GH, "ih"))
+            self._gemms(wg, s)
+            if dxp or tail:
+                self._gemms(dxp + tail, s)
+            if on_layer is not None:
+                on_layer(li)
+            dy_t, dy_ns, dy_stride = lb["dx"], nx, M * K
+            dy_ptr = dy_t.data_ptr()
+            if li == 0 and n.src[0] == "node":
+                n.src[1].gsrc = (lb["dx"], nx, M * K)
+            elif li == 0 and self.want_dx:
+                self._rec_slab_sum_ptr(lb["dx"].data_ptr(), nx, M * K, M * K, self.ext_dx, s)
+
     def _rec_fwd(self, n, s, train):
+        if getattr(n, "std", False):
+            return self._std_fwd(n, s, train)
         M, T = self.M, self.T
         self._quant_chain(n, s)
         for li, (sp, lb) in enumerate(zip(n.layers, n.lbuf)):
@@ -2572,6 +2804,8 @@ class Engine:
     def _rec_bwd(self, n, s, want_dx0=False, on_layer=None):
         """BPTT of a recurrent node, top layer first; on_layer(li) after layer li's weight
         gradients are queued (the data-parallel bucket cut)."""
+        if getattr(n, "std", False):
+            return self._std_bwd(n, s, want_dx0=want_dx0, on_layer=on_layer)
         M, T = self.M, self.T
         gs = getattr(n, "gsrc", None)
         if gs is not None:                   # external mode: the caller's output gradient

@@ -943,3 +943,121 @@ class LSTM(_PatternSet, nn.Module):
                               pattern=bool(self.if_pattern), ln=bool(self.lstm_use_laynorm[i]),
                               ln_gamma=self.ln[i].gamma, ln_beta=self.ln[i].beta))
         return specs
+
+
+class _StdParams(nn.Module):
+    """The parameters of a torch.nn.LSTM / GRU / RNN as plain Parameters under torch's names, in
+    torch's registration order (weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, ..._l0_reverse,
+    ..._l1, ...) and with nn.RNNBase.reset_parameters' draws (U(-1/sqrt(H), 1/sqrt(H)) in that
+    order).  Plain Parameters, not a wrapped nn.LSTM: its flatten_parameters() may re-seat the
+    parameter storage on .to(device), while the engine keeps device pointers, and its own forward
+    (MIOpen) must never run."""
+
+    def __init__(self, G, inp, H, layers, bias, ndir):
+        super().__init__()
+        for l in range(layers):
+            K = inp if l == 0 else H * ndir
+            for d in range(ndir):
+                sfx = "_l%d%s" % (l, "_reverse" if d else "")
+                self.register_parameter("weight_ih" + sfx, nn.Parameter(torch.empty(G * H, K)))
+                self.register_parameter("weight_hh" + sfx, nn.Parameter(torch.empty(G * H, H)))
+                if bias:
+                    self.register_parameter("bias_ih" + sfx, nn.Parameter(torch.empty(G * H)))
+                    self.register_parameter("bias_hh" + sfx, nn.Parameter(torch.empty(G * H)))
+        stdv = 1.0 / math.sqrt(H) if H > 0 else 0
+        for p in self.parameters():
+            nn.init.uniform_(p, -stdv, stdv)
+
+
+class _StdRec(nn.Module):
+    """LSTM_cudnn / GRU_cudnn / RNN_cudnn (neural_networks.py:364-465; options per
+    proto/{LSTM,GRU,RNN}_cudnn.proto): torch.nn.LSTM / GRU / RNN with a zero initial state.  Each
+    direction has its own weights, the GRU is torch's cell (the reset gate multiplies after the
+    recurrent product), and dropout acts between layers — the standard-cell time loops of
+    pkc_rnn_std_fwd / _bwd, not the cells of the reference's own LSTM / GRU / RNN classes."""
+
+    seq_model = True
+    std_cell = ""           # "lstm" | "gru" | "rnn": also the attribute holding the parameters
+    STD_GATES = 0
+
+    def __init__(self, options, inp_dim):
+        super().__init__()
+        o, name = options, type(self).__name__
+        for k in o:
+            if any(w in k for w in ("hcgs", "quant", "prune", "pattern")):
+                raise NotImplementedError("%s: the key %s (CGS / quantisation / pruning) is not "
+                                          "supported, the reference class has no such hook" % (name, k))
+            if "laynorm" in k or "batchnorm" in k:
+                raise NotImplementedError("%s: the input normalisation key %s is not supported, the "
+                                          "reference class has none" % (name, k))
+        self.input_dim = inp_dim
+        self.hidden_size = int(o["hidden_size"])
+        self.num_layers = int(o["num_layers"])
+        self.bias = strtobool(o["bias"])
+        self.batch_first = strtobool(o["batch_first"])     # parsed and ignored, as the reference
+        self.dropout = float(o["dropout"])
+        self.bidirectional = strtobool(o["bidirectional"])
+        if not 0.0 <= self.dropout < 1.0:
+            raise ValueError("%s: dropout = %s is outside [0, 1)" % (name, o["dropout"]))
+        self.nonlinearity = "tanh"
+        if self.std_cell == "rnn":
+            self.nonlinearity = o["nonlinearity"]
+            if self.nonlinearity not in ("tanh", "relu"):
+                raise NotImplementedError("%s: nonlinearity = %s (tanh or relu)" % (name, self.nonlinearity))
+        self.to_do = o.get("to_do", "train")
+        self.prune = False
+        self.guided_hcgs = False
+        self.apply_guided_hcgs = False
+        self.if_pattern = False
+        self.skip_regularization = strtobool(o.get("skip_regularization", "False"))
+        nd = 2 if self.bidirectional else 1
+        setattr(self, self.std_cell, nn.ModuleList([_StdParams(
+            self.STD_GATES, inp_dim, self.hidden_size, self.num_layers, self.bias, nd)]))
+        self.out_dim = self.hidden_size * nd
+
+    def prune_parameters(self):
+        raise NotImplementedError("the reference %s has no prune hook" % type(self).__name__)
+
+    def forward(self, x):
+        """(T, B, F) -> (T, B, out_dim) on the pkc kernels, trainable under autograd (pkc.plugin)."""
+        return arch_forward(self, x)
+
+    def check_supported(self):
+        pass
+
+    def input_norm_specs(self):
+        return []
+
+    def layer_specs(self):
+        """Per layer: the packed per-direction weights (one projection matmul per direction gives
+        all gates) and the inter-layer dropout of its output (none after the last layer)."""
+        P = getattr(self, self.std_cell)[0]
+        nd = 2 if self.bidirectional else 1
+        specs = []
+        for l in range(self.num_layers):
+            sfx = ["_l%d%s" % (l, "_reverse" if d else "") for d in range(nd)]
+            get = lambda n: [getattr(P, n + s, None) for s in sfx]      # noqa: E731
+            specs.append(dict(std=self.std_cell, H=self.hidden_size, act=self.nonlinearity,
+                              bidir=bool(self.bidirectional), ndir=nd, bn=False, bnm=[], ln=False,
+                              drop=self.dropout if l < self.num_layers - 1 else 0.0,
+                              W=get("weight_ih"), U=get("weight_hh"), bih=get("bias_ih"),
+                              bhh=get("bias_hh"), Wmask=None, Umask=None, ibits=0, qbits=0))
+        return specs
+
+
+class LSTM_cudnn(_StdRec):
+    """neural_networks.py:364-397 (nn.LSTM; gate rows i, f, g, o).  Parameters lstm.0.*."""
+    std_cell = "lstm"
+    STD_GATES = 4
+
+
+class GRU_cudnn(_StdRec):
+    """neural_networks.py:400-430 (nn.GRU; gate rows r, z, n).  Parameters gru.0.*."""
+    std_cell = "gru"
+    STD_GATES = 3
+
+
+class RNN_cudnn(_StdRec):
+    """neural_networks.py:433-465 (nn.RNN, nonlinearity tanh | relu).  Parameters rnn.0.*."""
+    std_cell = "rnn"
+    STD_GATES = 1
