@@ -496,13 +496,18 @@ typedef struct {
    * forward; g (T, B2, H) the post-norm gradients, dgamma / dbeta (H) written by the backward. */
   const float* ln_gamma; const float* ln_beta; float ln_eps;
   float* ln_xhat; float* ln_stat; float* ln_g; float* ln_dgamma; float* ln_dbeta;
-  /* Block-sparse U (static HCGS masks, HCGS.py:24-28; liGRU / LSTM, no quantised h): per
-   * workgroup tile, the indices of the 16-wide contraction blocks holding a nonzero of the mask
-   * (-1 = empty slot), kmap_s* slots per tile (16, 32 or 64; 16 lane groups x kmap_s/16 blocks).
-   *   kmap_fwd [ceil(H / (16/G))][kmap_s_fwd]: blocks of k (h_{t-1} / U columns) that the forward
-   *     tile of 16/G units x G gates reads;
+  /* Block-sparse U (static HCGS masks, HCGS.py:24-28; every cell, no quantised h; the RNN with
+   * fp32 step products only): per workgroup tile, the indices of the 16-wide contraction blocks
+   * holding a nonzero of the mask (-1 = empty slot: never read, a tile whose row is all -1 gives a
+   * zero product), kmap_s* slots per tile (16, 32 or 64; 16 lane groups x kmap_s/16 blocks).
+   *   kmap_fwd, one-phase cells (liGRU, LSTM, RNN) [ceil(H / (16/G))][kmap_s_fwd]: blocks of k
+   *     (h_{t-1} / U columns) that the forward tile of 16/G units x G gates reads;
+   *   kmap_fwd, two-phase cells (GRU, minimalGRU; NG = G - 1 gates read h_{t-1}): ONE allocation,
+   *     first the phase-0 table [ceil(H / (16/NG))][kmap_s_fwd] (tiles of 16/NG units x NG gates),
+   *     then the phase-1 table [ceil(H/16)][kmap_s_fwd] (tiles of 16 units of the candidate gate's
+   *     U, whose contraction runs over r*h / z*h), both with the same kmap_s_fwd;
    *   kmap_bwd [G][ceil(H/16)][kmap_s_bwd]: blocks of j (U rows) that the BPTT tile of 16 columns k
-   *     of gate g reads.
+   *     of gate g reads (two-phase cells: the candidate gate's table serves its d(r*h) product).
    * NULL: dense contraction over all H. */
   const int32_t* kmap_fwd; const int32_t* kmap_bwd; int kmap_s_fwd, kmap_s_bwd;
   /* bf16 step products (the performance mode of the sequence configs; liGRU / LSTM / RNN, dense U,

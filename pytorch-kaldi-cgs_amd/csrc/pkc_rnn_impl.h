@@ -770,6 +770,9 @@ __device__ __forceinline__ void cand_epi(const pkc_rnn_args& a, const RnnIdx& ix
 // NW waves (4: 256 threads, or 8: the contraction in 32 strips of S — half the operand loads per
 // lane and half the MFMA chain per wave, for the long-H layers whose step is load-latency-bound)
 // BF: bf16 step product (step_bf16: hs_h / U_h operands, mfma_chain_h)
+// SP: block-sparse U (pkc_rnn_args.kmap_fwd): the lane groups read the 16-wide contraction blocks
+// their tile's kmap row lists instead of 16 contiguous strips; both phases of the two-phase cells
+// (the candidate's table follows the phase-0 table) and the one-gate RNN tile included
 // QX (quantised h, pkc_rnn_args.qh_exact): U is on an 8-bit grid (m / 128, |m| <= 128: exact in
 // bf16, U_h) and q_g = RN(k var_s) with integers |k| <= 2^15, so U q_g = var_s U k up to the one
 // rounding of each q: k = 256 kh + kl (|kh| <= 128, |kl| <= 255, both exact in bf16) and the two
@@ -843,9 +846,12 @@ __global__ __launch_bounds__(64 * NW) void rnn_fwd_mm(pkc_rnn_args a, int t, int
   float va[S], vb[S], vu[QX ? 1 : S];
   rbf16x8 hu[QX ? S / 8 : 1];
   if constexpr (SP) {
-    static_assert(!QH && PH == 0, "block-sparse U: no quantised h, one-phase cells");
+    static_assert(!QH, "block-sparse U: no quantised h");
+    // two-phase cells: the candidate's table follows the phase-0 table's ceil(H / NU0) rows
+    constexpr int NU0 = 16 / (two_phase(CELL) ? cell_gates(CELL) - 1 : NG);
+    const int64_t row = PH == 0 ? bx : (H + NU0 - 1) / NU0 + bx;
     int blk[S / 16];
-    tile_blocks<S>(a.kmap_fwd + (int64_t)bx * S, blk);
+    tile_blocks<S>(a.kmap_fwd + row * S, blk);
     load_blocks<S>(src + (int64_t)(ra < B2 ? ra : 0) * H, ra < B2, blk, H, vw, va);
     if constexpr (!R16) load_blocks<S>(src + (int64_t)(rb < B2 ? rb : 0) * H, rb < B2, blk, H, vw, vb);
     load_blocks<S>(pu, u < H, blk, H, vw, vu);
@@ -1069,6 +1075,8 @@ __device__ __forceinline__ void rh_epi(const pkc_rnn_args& a, const RnnIdx& ix, 
 // MODE 0: the product of gate g0 + blockIdx.z into slab blockIdx.z (a.work + (4 + z) n);
 // MODE 1: one-gate product + bwd_step_epi (t = tt + 1); MODE 2: one-gate product + rh_epi.
 // out[r][k] = sum_j dg_g[t][r][j] * U_g[j][k], B operand from U^T (a.ut, G x H x H).
+// SP: block-sparse U in every MODE — the tile (gate g, 16 columns k) reads the U-row blocks j of
+// its kmap_bwd row; the candidate's product (MODE 2) goes on through r / z as the dense form's.
 template <int G, int CELL, int MODE, int S, bool SP = false, int NW = 4, bool R16 = false,
           bool BF = false>
 __global__ __launch_bounds__(64 * NW) void rnn_bwd_mm(pkc_rnn_args a, int t, int g0, int vw) {
@@ -1110,8 +1118,7 @@ __global__ __launch_bounds__(64 * NW) void rnn_bwd_mm(pkc_rnn_args a, int t, int
   } else {
   float va[S], vb[S], vu[S];
   if constexpr (SP) {
-    static_assert(MODE == 0, "block-sparse U: gate-split BPTT products only");
-    int blk[S / 16];
+    int blk[S / 16];                  // (table [G][ceil(H/16)][S]: g = g0 of the one-gate modes)
     tile_blocks<S>(a.kmap_bwd + ((int64_t)g * gridDim.x + bx) * S, blk);
     load_blocks<S>(dg + (int64_t)(ra < B2 ? ra : 0) * H, ra < B2, blk, H, vw, va);
     if constexpr (!R16) load_blocks<S>(dg + (int64_t)(rb < B2 ? rb : 0) * H, rb < B2, blk, H, vw, vb);
@@ -1233,13 +1240,13 @@ static int fwd_impl_s(const pkc_rnn_args* a, hipStream_t s) {
     const dim3 g1r(g1.x, rows_16), g2r(g2.x, rows_16);
     for (int t = 0; t < a->T; ++t) {
       if (r16) {
-        hipLaunchKernelGGL((rnn_fwd_mm<NG, CELL, 0, S, false, false, 4, true>), g1r, dim3(RT), 0, s,
+        hipLaunchKernelGGL((rnn_fwd_mm<NG, CELL, 0, S, false, SP, 4, true>), g1r, dim3(RT), 0, s,
                            *a, t, vw);
-        hipLaunchKernelGGL((rnn_fwd_mm<1, CELL, 1, S, false, false, 4, true>), g2r, dim3(RT), 0, s,
+        hipLaunchKernelGGL((rnn_fwd_mm<1, CELL, 1, S, false, SP, 4, true>), g2r, dim3(RT), 0, s,
                            *a, t, vw);
       } else {
-        hipLaunchKernelGGL((rnn_fwd_mm<NG, CELL, 0, S, false>), g1, dim3(RT), 0, s, *a, t, vw);
-        hipLaunchKernelGGL((rnn_fwd_mm<1, CELL, 1, S, false>), g2, dim3(RT), 0, s, *a, t, vw);
+        hipLaunchKernelGGL((rnn_fwd_mm<NG, CELL, 0, S, false, SP>), g1, dim3(RT), 0, s, *a, t, vw);
+        hipLaunchKernelGGL((rnn_fwd_mm<1, CELL, 1, S, false, SP>), g2, dim3(RT), 0, s, *a, t, vw);
       }
       if (a->ln_gamma) hipLaunchKernelGGL(rnn_ln_fwd, dim3((B2 + 3) / 4), dim3(256), 0, s, *a, t);
     }
@@ -1266,17 +1273,24 @@ static int fwd_impl_s(const pkc_rnn_args* a, hipStream_t s) {
     }
     for (int t = 0; t < a->T; ++t) {
       if constexpr (SP) {
-        if (r16 && a->step_bf16)
-          hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true, 4, true, true>), g16, nt, 0, s,
-                             *a, t, vw);
-        else if (r16)
-          hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true, 4, true>), g16, nt, 0, s, *a,
-                             t, vw);
-        else if (a->step_bf16)
-          hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true, 4, false, true>), g1, nt, 0, s,
-                             *a, t, vw);
-        else
-          hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true>), g1, nt, 0, s, *a, t, vw);
+        bool bf = false;
+        if constexpr (CELL != PKC_CELL_RNN) {   // (check(): the RNN has no block-sparse bf16 form)
+          if ((bf = a->step_bf16 != 0)) {
+            if (r16)
+              hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true, 4, true, true>), g16, nt, 0,
+                                 s, *a, t, vw);
+            else
+              hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true, 4, false, true>), g1, nt, 0,
+                                 s, *a, t, vw);
+          }
+        }
+        if (!bf) {
+          if (r16)
+            hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true, 4, true>), g16, nt, 0, s, *a,
+                               t, vw);
+          else
+            hipLaunchKernelGGL((rnn_fwd_mm<G, CELL, 0, S, false, true>), g1, nt, 0, s, *a, t, vw);
+        }
       } else if (r16 && a->qbits > 0) {
         bool done = false;
         if constexpr (CELL == PKC_CELL_LSTM && WS % 8 == 0)
@@ -1330,29 +1344,29 @@ static int bwd_impl_s(const pkc_rnn_args* a, float* dpre, hipStream_t s) {
     // the candidate gate's U^T product (MODE 2) and the gates' sum (MODE 0 / 1)
     auto mm2 = [&](int t) {
       if (r16)
-        hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 2, S, false, 4, true>), dim3(kt, rows_16, 1),
+        hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 2, S, SP, 4, true>), dim3(kt, rows_16, 1),
                            dim3(RT), 0, s, *a, t, HG, vw);
       else
-        hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 2, S>), dim3(kt, rows, 1), dim3(RT), 0, s, *a, t,
-                           HG, vw);
+        hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 2, S, SP>), dim3(kt, rows, 1), dim3(RT), 0, s, *a,
+                           t, HG, vw);
     };
     mm2(a->T - 1);
     for (int tt = a->T - 2; tt >= 0; --tt) {
       if constexpr (CELL == PKC_CELL_GRU) {           // Uz^T dz + Ur^T dr: two gate slabs
         if (r16)
-          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S, false, 4, true>), dim3(kt, rows_16, 2),
+          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S, SP, 4, true>), dim3(kt, rows_16, 2),
                              dim3(RT), 0, s, *a, tt + 1, 0, vw);
         else
-          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S>), dim3(kt, rows, 2), dim3(RT), 0, s, *a,
-                             tt + 1, 0, vw);
+          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 0, S, SP>), dim3(kt, rows, 2), dim3(RT), 0, s,
+                             *a, tt + 1, 0, vw);
         hipLaunchKernelGGL((rnn_bwd_epi<G, CELL, 2>), dim3(eb), dim3(256), 0, s, *a, tt);
       } else {                                        // minimalGRU: Uz^T dz, one gate
         if (r16)
-          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S, false, 4, true>), dim3(kt, rows_16, 1),
+          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S, SP, 4, true>), dim3(kt, rows_16, 1),
                              dim3(RT), 0, s, *a, tt + 1, 0, vw);
         else
-          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S>), dim3(kt, rows, 1), dim3(RT), 0, s, *a,
-                             tt + 1, 0, vw);
+          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S, SP>), dim3(kt, rows, 1), dim3(RT), 0, s,
+                             *a, tt + 1, 0, vw);
       }
       if (ln) hipLaunchKernelGGL((rnn_ln_bwd_gates<G, CELL>), lg, dim3(256), 0, s, *a, tt);
       mm2(tt);
@@ -1390,10 +1404,10 @@ static int bwd_impl_s(const pkc_rnn_args* a, float* dpre, hipStream_t s) {
     for (int tt = a->T - 2; tt >= 0; --tt) {
       if constexpr (G == 1) {
         if (r16)
-          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S, false, 4, true>), gg, dim3(RT), 0, s, *a,
+          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S, SP, 4, true>), gg, dim3(RT), 0, s, *a,
                              tt + 1, 0, vw);
         else
-          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S>), gg, dim3(RT), 0, s, *a, tt + 1, 0, vw);
+          hipLaunchKernelGGL((rnn_bwd_mm<G, CELL, 1, S, SP>), gg, dim3(RT), 0, s, *a, tt + 1, 0, vw);
       } else {
         bool bf = false;
         if constexpr (SP) {                           // block-sparse U with bf16 step products
@@ -1479,12 +1493,10 @@ static int fwd_impl(const pkc_rnn_args* a, hipStream_t s) {
     case 3: return rnn_ligru_grid_fwd(a, s);
     default: break;                            // one launch per step
   }
-  if constexpr (!two_phase(CELL) && G > 1) {
-    if (a->kmap_fwd) {
-      if (a->kmap_s_fwd == 16) return fwd_impl_s<G, CELL, 16, true>(a, s);
-      if (a->kmap_s_fwd == 32) return fwd_impl_s<G, CELL, 32, true>(a, s);
-      return fwd_impl_s<G, CELL, 64, true>(a, s);
-    }
+  if (a->kmap_fwd) {                           // block-sparse U (every cell; check())
+    if (a->kmap_s_fwd == 16) return fwd_impl_s<G, CELL, 16, true>(a, s);
+    if (a->kmap_s_fwd == 32) return fwd_impl_s<G, CELL, 32, true>(a, s);
+    return fwd_impl_s<G, CELL, 64, true>(a, s);
   }
   return PKC_S_DISPATCH(fwd_impl_s, a, s);
 }
@@ -1505,12 +1517,10 @@ static int bwd_impl(const pkc_rnn_args* a, float* dpre, hipStream_t s) {
     PKC_LAUNCH_CHECK("pkc_rnn_bwd fold");
     return PKC_OK;
   }
-  if constexpr (!two_phase(CELL) && G > 1) {
-    if (a->kmap_bwd) {
-      if (a->kmap_s_bwd == 16) return bwd_impl_s<G, CELL, 16, true>(a, dpre, s);
-      if (a->kmap_s_bwd == 32) return bwd_impl_s<G, CELL, 32, true>(a, dpre, s);
-      return bwd_impl_s<G, CELL, 64, true>(a, dpre, s);
-    }
+  if (a->kmap_bwd) {
+    if (a->kmap_s_bwd == 16) return bwd_impl_s<G, CELL, 16, true>(a, dpre, s);
+    if (a->kmap_s_bwd == 32) return bwd_impl_s<G, CELL, 32, true>(a, dpre, s);
+    return bwd_impl_s<G, CELL, 64, true>(a, dpre, s);
   }
   return PKC_S_DISPATCH(bwd_impl_s, a, dpre, s);
 }
@@ -1553,8 +1563,9 @@ static int bwd_impl(const pkc_rnn_args* a, float* dpre, hipStream_t s) {
     for (int g = 0; g < G; ++g) PKC_CHECK_ARG(a->U_h[g], "pkc_rnn: qh_exact needs U_h[%d]", g);
   }
   if (a->kmap_fwd || a->kmap_bwd) {
-    PKC_CHECK_ARG((a->cell == PKC_CELL_LIGRU || a->cell == PKC_CELL_LSTM) && a->qbits <= 0,
-                  "pkc_rnn: block-sparse U only for liGRU / LSTM without quantised h");
+    PKC_CHECK_ARG(a->qbits <= 0, "pkc_rnn: block-sparse U only without quantised h");
+    PKC_CHECK_ARG(a->cell != PKC_CELL_RNN || !a->step_bf16,
+                  "pkc_rnn: the RNN's block-sparse U has fp32 step products only");
     const int sf = a->kmap_s_fwd, sb = a->kmap_s_bwd;
     PKC_CHECK_ARG(!a->kmap_fwd || sf == 16 || sf == 32 || sf == 64, "pkc_rnn: kmap_s_fwd %d", sf);
     PKC_CHECK_ARG(!a->kmap_bwd || sb == 16 || sb == 32 || sb == 64, "pkc_rnn: kmap_s_bwd %d", sb);

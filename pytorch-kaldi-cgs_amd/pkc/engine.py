@@ -1467,17 +1467,19 @@ class Engine:
         return t[1 if dx else 0] if t is not None else None
 
     def _build_kmaps(self):
-        """Block-sparse U for static HCGS masks (liGRU / LSTM; no prune, pattern or quantised h,
-        whose zeros move): per step-kernel tile, the 16-wide contraction blocks that hold a
-        nonzero of the mask (pkc_rnn_args.kmap_*).  The optimizer keeps masked entries at zero, so
+        """Block-sparse U for static HCGS masks (every cell of pkc_rnn_args; no prune, pattern or
+        quantised h, whose zeros move): per step-kernel tile, the 16-wide contraction blocks that
+        hold a nonzero of the mask (pkc_rnn_args.kmap_*).  The optimizer keeps masked entries at zero, so
         skipping the other blocks changes only the order of the fp32 sums."""
         for n in self.nodes:
-            if not n.rec or n.cell not in (L.CELL_LIGRU, L.CELL_LSTM):
+            if not n.rec or n.cell is None:
                 continue
             for sp, lb in zip(n.layers, n.lbuf):
                 lb["kmap_fwd"] = lb["kmap_bwd"] = None
                 if RNN_SPARSE == "off" or sp.get("prune") is not None or sp["ibits"]:
                     continue
+                if n.cell == L.CELL_RNN and lb.get("hs_h") is not None:
+                    continue        # bf16 mode: the RNN keeps its dense bf16 steps (no sparse form)
                 um = [sp["Umasks"][g] if sp.get("Umasks") else sp["Umask"] for g in range(n.G)]
                 if any(m is None or id(U) in n.emask for m, U in zip(um, sp["U"])):
                     continue
@@ -1489,12 +1491,23 @@ class Engine:
                     mb[:H, :H] = (m.detach().reshape(H, H) != 0).float()
                     rowp.append(mb.view(nb * 16, nb, 16).amax(2) > 0)          # [row][col blk]
                     pres.append(mb.view(nb, 16, nb, 16).amax(dim=(1, 3)) > 0)  # [row blk][col blk]
-                NU = 16 // n.G
-                nt = -(-H // NU)
-                acc = torch.zeros(nt * NU, nb, dtype=torch.bool, device=self.dev)
-                for rp in rowp:
-                    acc[:H] |= rp[:H]
-                fwd = acc.view(nt, NU, nb).any(1)                   # [tile][k blk]
+                def fwd_tiles(gates):
+                    """[tile][k blk] of the forward tiles holding `gates` of 16 / len(gates) units"""
+                    NU = 16 // len(gates)
+                    nt = -(-H // NU)
+                    acc = torch.zeros(nt * NU, nb, dtype=torch.bool, device=self.dev)
+                    for g in gates:
+                        acc[:H] |= rowp[g][:H]
+                    return acc.view(nt, NU, nb).any(1)
+
+                if n.cand is None:
+                    fwd = fwd_tiles(range(n.G))
+                else:
+                    # two-phase cells: the phase-0 table (the gates that read h_{t-1}) and then the
+                    # phase-1 table (the candidate gate, 16 units a tile) in one allocation
+                    fwd = torch.cat([fwd_tiles([g for g in range(n.G) if g != n.cand]),
+                                     fwd_tiles([n.cand])])
+                nt = fwd.shape[0]
                 # BPTT tile (gate g, columns k-block kt) reads the row blocks j with a nonzero
                 bwd = torch.stack([p_.t() for p_ in pres])          # [g][kt][j blk]
                 dense_s = 16 if H <= 256 else 32 if H <= 512 else 48 if H <= 768 else 64 if H <= 1024 else 128

@@ -475,6 +475,22 @@ class SincNet(_ConvArch):
         return specs
 
 
+def _hcgs_hook_opts(net, o, key):
+    """The LSTM's HCGS hook on a cell the reference gives none (GRU, minimalGRU, RNN; the liGRU's
+    ``ligru_hcgs`` is the same extension): with ``key`` set, the keys hcgsx_* / hcgsh_* and the
+    mask lists hcgsx / hcgsh, registered before the layer lists as the LSTM's are
+    (neural_networks.py:548-550).  One W mask and one U mask per layer, shared by its gates
+    (:858-861, 980-983).  Without the key nothing is registered and nothing is drawn."""
+    net.hcgs_on = bool(strtobool(o.get(key, "False")))
+    setattr(net, key, net.hcgs_on)
+    if net.hcgs_on:
+        net.hcgsx_block = _lst(o, "hcgsx_block", int)
+        net.hcgsh_block = _lst(o, "hcgsh_block", int)
+        net.hcgsx_sparse = _lst(o, "hcgsx_sparse", float)
+        net.hcgsh_sparse = _lst(o, "hcgsh_sparse", float)
+        net.hcgsx, net.hcgsh = nn.ModuleList(), nn.ModuleList()
+
+
 class liGRU(nn.Module):
     """neural_networks.py:1429-1599 (options per proto/liGRU.proto).  Parameters: wh, wz (input
     Linear), uh, uz (recurrent Linear, no bias), bn_wh, bn_wz, ln; same names and init draws."""
@@ -571,7 +587,8 @@ class liGRU(nn.Module):
 
 class GRU(nn.Module):
     """neural_networks.py:1240-1426 (options per proto/GRU.proto).  Parameters: wh, uh, wz, uz, wr,
-    ur, ln, bn_wh, bn_wz, bn_wr (registration order and init draws of the reference)."""
+    ur, ln, bn_wh, bn_wz, bn_wr (registration order and init draws of the reference).  pkc adds the
+    optional HCGS hook ``gru_hcgs`` (_hcgs_hook_opts); without the key nothing else is registered."""
 
     seq_model = True
     cell = "gru"
@@ -597,6 +614,8 @@ class GRU(nn.Module):
         self.apply_guided_hcgs = False
         self.if_pattern = False
         self.skip_regularization = strtobool(o.get("skip_regularization", "False"))
+        # pkc extension (as ligru_hcgs; no reference counterpart): the LSTM's HCGS hook on the GRU
+        _hcgs_hook_opts(self, o, "gru_hcgs")
         self.wh, self.uh = nn.ModuleList(), nn.ModuleList()
         self.wz, self.uz = nn.ModuleList(), nn.ModuleList()
         self.wr, self.ur = nn.ModuleList(), nn.ModuleList()
@@ -612,9 +631,13 @@ class GRU(nn.Module):
             self.wh.append(nn.Linear(cur, n, bias=add_bias))
             self.wz.append(nn.Linear(cur, n, bias=add_bias))
             self.wr.append(nn.Linear(cur, n, bias=add_bias))
+            if self.hcgs_on:
+                self.hcgsx.append(_Mask(hcgs_mask(n, cur, self.hcgsx_block, self.hcgsx_sparse)))
             self.uh.append(nn.Linear(n, n, bias=False))
             self.uz.append(nn.Linear(n, n, bias=False))
             self.ur.append(nn.Linear(n, n, bias=False))
+            if self.hcgs_on:
+                self.hcgsh.append(_Mask(hcgs_mask(n, n, self.hcgsh_block, self.hcgsh_sparse)))
             if self.gru_orthinit:
                 nn.init.orthogonal_(self.uh[i].weight)
                 nn.init.orthogonal_(self.uz[i].weight)
@@ -649,13 +672,16 @@ class GRU(nn.Module):
                               b=[self.wz[i].bias, self.wr[i].bias, self.wh[i].bias],
                               U=[self.uz[i].weight, self.ur[i].weight, self.uh[i].weight],
                               bnm=[self.bn_wz[i], self.bn_wr[i], self.bn_wh[i]],
-                              Wmask=None, Umask=None, ln=bool(self.gru_use_laynorm[i]),
+                              Wmask=self.hcgsx[i].mask if self.hcgs_on else None,
+                              Umask=self.hcgsh[i].mask if self.hcgs_on else None,
+                              ln=bool(self.gru_use_laynorm[i]),
                               ln_gamma=self.ln[i].gamma, ln_beta=self.ln[i].beta))
         return specs
 
 
 class _PlainRec(nn.Module):
-    """Shared construction of the reference's hook-free recurrent families (minimalGRU, RNN):
+    """Shared construction of the reference's hook-free recurrent families (minimalGRU, RNN;
+    pkc adds the optional HCGS hook minimalgru_hcgs / rnn_hcgs, see _hcgs_hook_opts):
     option keys <prefix>_lay/_drop/_use_batchnorm/..., input Linears w<g> (bias only without
     BN/LN), recurrent Linears u<g> (no bias, optional orthogonal init), bn_w<g>, ln."""
 
@@ -683,6 +709,8 @@ class _PlainRec(nn.Module):
         self.apply_guided_hcgs = False
         self.if_pattern = False
         self.skip_regularization = strtobool(o.get("skip_regularization", "False"))
+        # pkc extension (as ligru_hcgs; no reference counterpart): minimalgru_hcgs / rnn_hcgs
+        _hcgs_hook_opts(self, o, p + "_hcgs")
         for g in self.INIT_ORDER:
             setattr(self, "w" + g, nn.ModuleList())
             setattr(self, "u" + g, nn.ModuleList())
@@ -698,8 +726,12 @@ class _PlainRec(nn.Module):
             add_bias = not (self.use_ln[i] or self.use_bn[i])
             for g in self.INIT_ORDER:
                 getattr(self, "w" + g).append(nn.Linear(cur, n, bias=add_bias))
+            if self.hcgs_on:
+                self.hcgsx.append(_Mask(hcgs_mask(n, cur, self.hcgsx_block, self.hcgsx_sparse)))
             for g in self.INIT_ORDER:
                 getattr(self, "u" + g).append(nn.Linear(n, n, bias=False))
+            if self.hcgs_on:
+                self.hcgsh.append(_Mask(hcgs_mask(n, n, self.hcgsh_block, self.hcgsh_sparse)))
             if self.orthinit:
                 for g in self.INIT_ORDER:
                     nn.init.orthogonal_(getattr(self, "u" + g)[i].weight)
@@ -732,7 +764,9 @@ class _PlainRec(nn.Module):
                               b=[getattr(self, "w" + g)[i].bias for g in self.GATES],
                               U=[getattr(self, "u" + g)[i].weight for g in self.GATES],
                               bnm=[getattr(self, "bn_w" + g)[i] for g in self.GATES],
-                              Wmask=None, Umask=None, ln=bool(self.use_ln[i]),
+                              Wmask=self.hcgsx[i].mask if self.hcgs_on else None,
+                              Umask=self.hcgsh[i].mask if self.hcgs_on else None,
+                              ln=bool(self.use_ln[i]),
                               ln_gamma=self.ln[i].gamma, ln_beta=self.ln[i].beta))
         return specs
 
