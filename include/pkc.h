@@ -458,6 +458,26 @@ int pkc_feat_frontend(const float* raw, int D, int64_t Nout, const int32_t* src_
                       const float* scales, int order, int maxoff, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Raw-waveform framing (the `pkc-wav-frames` fea_opts stage; save_raw_fea.py:73-104 restated, an
+ * entry point added under ABI 9 without a struct change).  samples: the int16 audio of whole
+ * utterances; utterance u is samples[utt_beg[u] .. utt_beg[u] + utt_len[u]) with peak
+ * utt_peak[u] = max|s| in 1..32768.  Output row r (of Nout, any order) is frame
+ * f = frame_of_row[r] of utterance u = utt_of_row[r]: with S = lab_wshift, Lw = lab_wlen (samples)
+ *   c = (2*f*S + Lw - 2) / 2,  b = c - W/2,
+ *   out[r][j] = 0 <= b + j < len_u ? (float)((double)s_u[b + j] / (double)peak_u) : 0.0f.
+ * sig_work: one float per sample of `samples` (the normalised signal, written by the first of the
+ * two launches: row r normalises the samples of its own frame — [f*S, (f+1)*S), to the end of the
+ * utterance for its last frame — so the row maps must name every frame of each utterance they
+ * name, as the loader's and the writer's do; frames are those with f*S + Lw < len_u).
+ * out: Nout x W; rows are written as 16-byte stores when W % 4 == 0.  W even and > 0, Lw >= 2,
+ * S >= 1; Nout == 0 launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+int pkc_wav_frames(const int16_t* samples, const int64_t* utt_beg, const int32_t* utt_len,
+                   const int32_t* utt_peak, const int32_t* utt_of_row, const int32_t* frame_of_row,
+                   int64_t Nout, int W, int lab_wlen, int lab_wshift, float* sig_work, float* out,
+                   void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Recurrent layers: the per-time-step loops of liGRU (neural_networks.py:1573-1584), LSTM
  * (neural_networks.py:1077-1097), GRU (:1390-1396, gates z, r, h), minimalGRU (:1751-1755, gates
  * z, h) and RNN (:1905-1907, gate h).  wpre holds the gate pre-activations W x (+BN) for the T*B input

@@ -317,22 +317,31 @@ class StagedChunk:
 
     With a Kaldi front-end (pkc.frontend.FeaFrontend: apply-cmvn / add-deltas), whole utterances
     are uploaded in their own order and pkc_feat_frontend writes the processed frames in the
-    sorted / split order on the same stream."""
+    sorted / split order on the same stream.
 
-    def __init__(self, names, raw, lab_arrays, end_index, device, fe_args=None):
+    With a wav-list stream (pkc.frontend.WavFrames) the upload is the utterances' int16 samples
+    and pkc_wav_frames cuts the (N, W) matrix of overlapping windows from them, on that stream."""
+
+    def __init__(self, names, raw, lab_arrays, end_index, device, fe_args=None, wav_args=None):
         self.names, self.lab_arrays, self.end_index = names, lab_arrays, end_index
         dev = torch.device(device)
         self.stream = torch.cuda.Stream(device=dev)
-        host = [raw] + ([] if fe_args is None else list(fe_args["arrays"]))
-        pinned = []
-        for a in host:
-            t = torch.empty(a.shape, dtype=torch.float32 if a.dtype == np.float32 else torch.int32,
-                            pin_memory=True)
-            t.numpy()[...] = a
-            pinned.append(t)
+        if wav_args is not None:
+            pinned = wav_args["pinned"]
+        else:
+            host = [raw] + ([] if fe_args is None else list(fe_args["arrays"]))
+            pinned = []
+            for a in host:
+                t = torch.empty(a.shape, dtype=torch.float32 if a.dtype == np.float32 else torch.int32,
+                                pin_memory=True)
+                t.numpy()[...] = a
+                pinned.append(t)
         with torch.cuda.stream(self.stream):
             dev_t = [t.to(dev, non_blocking=True) for t in pinned]
-            if fe_args is None:
+            if wav_args is not None:
+                self.raw_d, work = wav_frames_device(dev_t, wav_args["wav"], self.stream)
+                self._dev_inputs = dev_t + [work]
+            elif fe_args is None:
                 self.raw_d = dev_t[0]
             else:
                 raw_src, srow, urow, ubeg, uend, unorm, norm, scales = dev_t
@@ -379,7 +388,68 @@ def frontend_args(fea, pieces, frontend):
                 out_shape=(len(srow), frontend.out_dim(D)))
 
 
+def wav_args(sig, pieces, wav):
+    """Host tables of pkc_wav_frames for these pieces, in pinned memory: every utterance's int16
+    samples in one buffer (each utterance whole, in order of first use), per-utterance sample
+    offset / length / peak, per-output-row utterance and frame.  sig: {utt: (samples, peak)}."""
+    keys = list(dict.fromkeys(k for k, _, _ in pieces))
+    if not keys:
+        raise ValueError("empty chunk: no utterance survived the feature / label filters")
+    uid = {k: i for i, k in enumerate(keys)}
+    lens = np.array([len(sig[k][0]) for k in keys], dtype=np.int64)
+    ubeg = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    nrows = sum(b - a for _, a, b in pieces)
+    if nrows >= 2 ** 31 or int(lens.max()) >= 2 ** 30:
+        raise ValueError("chunk too large for the int32 front-end row maps")
+
+    def pin(shape, dtype):
+        return torch.empty(shape, dtype=dtype, pin_memory=True)
+    samples = pin((int(lens.sum()),), torch.int16)
+    buf = samples.numpy()
+    for k, o in zip(keys, ubeg):
+        buf[o:o + len(sig[k][0])] = sig[k][0]
+    tabs = [(ubeg, torch.int64), (lens, torch.int32),
+            (np.array([sig[k][1] for k in keys]), torch.int32),
+            (np.concatenate([np.full(b - a, uid[k]) for k, a, b in pieces]), torch.int32),
+            (np.concatenate([np.arange(a, b) for _, a, b in pieces]), torch.int32)]
+    pinned = [samples]
+    for a, dt in tabs:
+        t = pin(a.shape, dt)
+        t.numpy()[...] = a
+        pinned.append(t)
+    return dict(pinned=pinned, wav=wav)
+
+
+def wav_frames_device(dev_t, wav, stream):
+    """pkc_wav_frames over the device copies of wav_args' tables on `stream` (the current one):
+    the (rows, W) float32 matrix and the normalised-signal work buffer it was gathered from."""
+    samples, ubeg, ulen, upeak, urow, frow = dev_t
+    out = torch.empty(urow.numel(), wav.W, dtype=torch.float32, device=samples.device)
+    work = torch.empty(samples.numel(), dtype=torch.float32, device=samples.device)
+    call("pkc_wav_frames", ptr(samples), ptr(ubeg), ptr(ulen), ptr(upeak), ptr(urow), ptr(frow),
+         urow.numel(), wav.W, wav.Lw, wav.S, ptr(work), ptr(out), C.c_void_p(stream.cuda_stream))
+    return out, work
+
+
+def frame_signals(sig, wav, device="cuda"):
+    """Every frame of every utterance of sig ({utt: (int16 samples, peak)}, in its order) on the
+    current stream -> (rows, W) float32 device matrix, utterance after utterance."""
+    pieces = [(k, 0, wav.check(k, len(s))) for k, (s, _) in sig.items()]
+    wa = wav_args(sig, pieces, wav)
+    dev_t = [t.to(device, non_blocking=True) for t in wa["pinned"]]
+    out, _ = wav_frames_device(dev_t, wav, torch.cuda.current_stream(dev_t[0].device))
+    torch.cuda.current_stream(dev_t[0].device).synchronize()   # the pinned tables die with wa
+    return out
+
+
 def stage_chunk(fea, labs, max_sequence_length, device="cuda", frontend=None):
+    if frontend is not None and frontend.wav is not None:
+        # fea: {utt: (int16 samples, peak)} of a wav list; the frames are cut on the GPU
+        wav = frontend.wav
+        names, pieces, lab_arrays, end_index = dataset_pieces(
+            {k: wav.n_frames(len(s)) for k, (s, _) in fea.items()}, labs, max_sequence_length)
+        return StagedChunk(names, None, lab_arrays, end_index, device,
+                           wav_args=wav_args(fea, pieces, wav))
     if frontend is None:
         names, raw, lab_arrays, end_index = load_dataset(fea, labs, max_sequence_length)
         return StagedChunk(names, np.ascontiguousarray(raw, dtype=np.float32), lab_arrays,

@@ -14,6 +14,10 @@ applies them to every frame on the GPU (pytorch-kaldi-cgs_amd/csrc/pkc_frontend.
 Kaldi itself is a third-party dependency that is not in /root/reference (no binaries, no fixture
 of its output), so this restatement is parity-UNPINNED against Kaldi; it is checked bit-exactly
 against the independent C restatement in oracle/kaldi_feat.c.
+
+A pkc extension stands beside them: the one-stage pipe ``pkc-wav-frames ... ark:- ark:- |`` makes
+fea_lst a wav list and cuts the raw-waveform frames of the reference's save_raw_fea.py on the GPU
+(``WavFrames``, pkc_wav_frames in csrc/pkc_wav.hip); that one is pinned to the script's own output.
 """
 import os
 import re
@@ -138,21 +142,109 @@ def delta_scales(order, window):
     return tab, maxoff
 
 
+WAV_STAGE = "pkc-wav-frames"
+
+
+class WavFrames:
+    """The ``pkc-wav-frames`` stage: the framing of the reference's save_raw_fea.py (:42-104) over
+    a wav list, so that a `raw` stream is read from the audio itself and not from an ark holding
+    every 200 ms window.  Window lengths in ms, rate in Hz (the script's constants by default);
+    sample counts are int(fs*ms/1000) as save_raw_fea.py:49-51."""
+
+    def __init__(self, sig_wlen=200, lab_wlen=25, lab_wshift=10, fs=16000):
+        self.sig_wlen, self.lab_wlen, self.lab_wshift, self.fs = sig_wlen, lab_wlen, lab_wshift, fs
+        self.W = int((fs * sig_wlen) / 1000)
+        self.Lw = int((fs * lab_wlen) / 1000)
+        self.S = int((fs * lab_wshift) / 1000)
+        if self.W < 1 or self.Lw < 2 or self.S < 1:
+            raise ValueError("%s: window of %d samples, label window of %d, shift of %d"
+                             % (WAV_STAGE, self.W, self.Lw, self.S))
+
+    def n_frames(self, n):
+        """Frames of an n-sample signal: the f >= 0 with f*S + Lw < n (save_raw_fea.py:84; strict,
+        so n = Lw + k*S has k frames, one fewer than Kaldi's 1 + (n - Lw) // S)."""
+        return -((self.Lw - n) // self.S) if n > self.Lw else 0
+
+    def frame_begin(self, f):
+        """First sample of frame f's window (negative: zeros in front), save_raw_fea.py:86-89."""
+        return (2 * f * self.S + self.Lw - 2) // 2 - self.W // 2
+
+    def check(self, utt, n):
+        """Refuse what the script cannot frame (never pad silently); returns the frame count."""
+        if self.W % 2:
+            raise ValueError("%s: utterance %s: an odd window of %d samples gives ragged rows in "
+                             "the reference" % (WAV_STAGE, utt, self.W))
+        F = self.n_frames(n)
+        if F == 0:
+            raise ValueError("%s: utterance %s: %d samples give no frame (label window %d)"
+                             % (WAV_STAGE, utt, n, self.Lw))
+        for f in range(F):
+            b = self.frame_begin(f)
+            if b >= 0:
+                break
+            if b + self.W > n:      # save_raw_fea.py:95-100: the slice assignment raises there
+                raise ValueError("%s: utterance %s: %d samples are too few, frame %d's window of "
+                                 "%d overflows the signal on both sides" % (WAV_STAGE, utt, n, f, self.W))
+        return F
+
+    def read(self, utt, path):
+        """Mono 16-bit PCM wav -> (int16 samples, peak max|s| in 1..32768), checked."""
+        import wave
+        with wave.open(path, "rb") as w:
+            if w.getnchannels() != 1:
+                raise ValueError("%s: utterance %s: %d channels in %s (mono only)"
+                                 % (WAV_STAGE, utt, w.getnchannels(), path))
+            if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
+                raise ValueError("%s: utterance %s: %d-byte samples in %s (16-bit PCM only)"
+                                 % (WAV_STAGE, utt, w.getsampwidth(), path))
+            if w.getframerate() != self.fs:
+                raise ValueError("%s: utterance %s: %s is sampled at %d Hz, --fs=%d"
+                                 % (WAV_STAGE, utt, path, w.getframerate(), self.fs))
+            s = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16)
+        return self.signal(utt, s)
+
+    def signal(self, utt, s):
+        """(samples, peak) of an int16 signal after the checks of `check`; an all-zero signal is
+        refused (the reference divides by its zero peak and trains on NaN)."""
+        s = np.ascontiguousarray(s, dtype=np.int16)
+        self.check(utt, len(s))
+        peak = max(int(s.max()), -int(s.min()))
+        if peak == 0:
+            raise ValueError("%s: utterance %s: the signal is all zero" % (WAV_STAGE, utt))
+        return s, peak
+
+
+def read_wav_list(path):
+    """``utt_id /path/file.wav`` per line (the list save_raw_fea.py reads) -> [(utt, wav path)]."""
+    out = []
+    with open(path) as f:
+        for line in f:
+            p = line.split(None, 1)
+            if len(p) == 2:
+                out.append((p[0], p[1].strip()))
+    return out
+
+
 class FeaFrontend:
-    """apply-cmvn / add-deltas stages of one fea_opts pipe."""
+    """apply-cmvn / add-deltas stages of one fea_opts pipe, or its one pkc-wav-frames stage."""
 
     def __init__(self):
         self.cmvn = None          # dict(stats={key: (2, D+1) f64}, utt2spk={utt: spk} | None, vars)
         self.order, self.window = 0, 2
+        self.wav = None           # WavFrames: fea_lst is a wav list
 
     @staticmethod
     def parse(fea_opts):
         """fea_opts -> FeaFrontend (None for an empty pipe).  Stages other than apply-cmvn and
-        add-deltas (and options Kaldi does not have) raise NotImplementedError."""
+        add-deltas (and options Kaldi does not have) raise NotImplementedError; so does
+        pkc-wav-frames beside any other stage or with an option it does not have."""
         fe = FeaFrontend()
         stages = [s.strip() for s in fea_opts.split("|") if s.strip()]
         if not stages:
             return None
+        if len(stages) > 1 and any(s.split()[0] == WAV_STAGE for s in stages):
+            raise NotImplementedError("fea_opts: %s frames a wav list and must be the only stage of "
+                                      "the pipe (got %s)" % (WAV_STAGE, " | ".join(stages)))
         for st in stages:
             argv = shlex.split(st)
             prog, args = argv[0], argv[1:]
@@ -162,7 +254,15 @@ class FeaFrontend:
             for o in opts:
                 k, _, v = o[2:].partition("=")
                 kv[k.replace("_", "-")] = v
-            if prog == "apply-cmvn":
+            if prog == WAV_STAGE:
+                unknown = set(kv) - {"sig-wlen", "lab-wlen", "lab-wshift", "fs"}
+                if unknown:
+                    raise NotImplementedError("%s options %s" % (WAV_STAGE, sorted(unknown)))
+                if pos != ["ark:-", "ark:-"]:
+                    raise NotImplementedError("%s %s: expected ark:- ark:-"
+                                              % (WAV_STAGE, " ".join(pos)))
+                fe.wav = WavFrames(**{k.replace("-", "_"): int(v) for k, v in kv.items()})
+            elif prog == "apply-cmvn":
                 if fe.cmvn is not None or fe.order:
                     raise NotImplementedError("fea_opts: apply-cmvn after add-deltas / twice")
                 unknown = set(kv) - {"utt2spk", "norm-vars", "norm-means", "reverse"}
@@ -228,7 +328,7 @@ def kaldi_on_path():
                for d in os.environ.get("PATH", "").split(os.pathsep) if d)
 
 
-_PIPE_RE = re.compile(r"^\s*(apply-cmvn|add-deltas)\b")
+_PIPE_RE = re.compile(r"^\s*(apply-cmvn|add-deltas|pkc-wav-frames)\b")
 
 
 def is_native_pipe(fea_opts):
