@@ -714,6 +714,12 @@ __global__ __launch_bounds__(FT) void dense_bwd_small_kernel(pkc_dense_bwd_args 
 // t + 12 and the block's partials are reduced over the 4 row-threads in the same order — with each
 // thread owning 4 adjacent columns (a block spans 256 columns): every column's arithmetic is the
 // scalar kernels' operation for operation, in one 16-byte access instead of four 4-byte ones.
+// Left to itself the compiler contracts other products in the two backward pairs (dy and dy * xhat
+// into the v4 stats sums only; the mean terms into the scalar apply pass only), a last-place
+// difference in a quarter of dz.  The v4 backward kernels therefore spell out which products are
+// fused, to the scalar kernels' compiled arithmetic; the scalar kernels, whose bits the engine's
+// recurrent tests are pinned to, are left as they are.  tests/test_gpu_dense_modes.py
+// (test_forms_agree_*) holds both pairs to the same bits.
 constexpr int EC4 = 64;   // float4 column groups per block
 
 __device__ __forceinline__ float4 z4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
@@ -873,11 +879,13 @@ __global__ __launch_bounds__(ET) void dense_bwd_stats_v4_kernel(pkc_dense_bwd_ar
       float4 d4;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
+        // as dense_bwd_stats_kernel compiles: y fused, the sums of the ROUNDED dy and dy * xhat
+#pragma clang fp contract(off)
         float g = f4get(g4, j);
         const uint8_t kj = j == 0 ? kp.x : (j == 1 ? kp.y : (j == 2 ? kp.z : kp.w));
         if (drop) g = kj ? g * scale : 0.f;
         const float xh = f4get(xh4, j);
-        const float y = bn ? xh * f4get(gam, j) + f4get(bet, j) : xh;
+        const float y = bn ? __builtin_fmaf(xh, f4get(gam, j), f4get(bet, j)) : xh;
         const float dy = g * act_bwd(a.act, y, act_fwd(a.act, y));
         f4set(d4, j, dy);
         f4set(sdy, j, f4get(sdy, j) + dy);
@@ -903,11 +911,12 @@ __global__ __launch_bounds__(ET) void dense_bwd_apply_v4_kernel(pkc_dense_bwd_ar
   if (c >= a.N || a.norm != PKC_NORM_BN_TRAIN) return;
   const int64_t N = a.N;
   const float* fin = part + (int64_t)((a.M + part_rows - 1) / part_rows) * 2 * N;
-  float k[4], mdy[4], mdyx[4];
+  float k[4], tdy[4], mdy[4], mdyx[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     k[j] = a.gamma[c + j] * a.save_invstd[c + j];
-    mdy[j] = fin[c + j] * invM;
+    tdy[j] = fin[c + j];
+    mdy[j] = tdy[j] * invM;
     mdyx[j] = fin[N + c + j] * invM;
   }
 #pragma unroll
@@ -918,7 +927,13 @@ __global__ __launch_bounds__(ET) void dense_bwd_apply_v4_kernel(pkc_dense_bwd_ar
     const float4 dz = ld4(a.dz + idx), xh = ld4(a.xhat + idx);
     float4 d;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) f4set(d, j, k[j] * (f4get(dz, j) - mdy[j] - f4get(xh, j) * mdyx[j]));
+    for (int j = 0; j < 4; ++j) {
+      // as dense_bwd_apply_kernel compiles: xhat * mean(dy xhat) taken off fused in every row, dz's
+      // mean fused (tdy * invM unrounded) in a thread's first row and rounded in the others
+#pragma clang fp contract(off)
+      const float t = i == 0 ? __builtin_fmaf(-invM, tdy[j], f4get(dz, j)) : f4get(dz, j) - mdy[j];
+      f4set(d, j, k[j] * __builtin_fmaf(-f4get(xh, j), mdyx[j], t));
+    }
     if (!a.dz_scratch) st4(a.dz + idx, d);
     if (a.dz_bf16) st_h4(a.dz_bf16, idx, d);
   }
@@ -952,6 +967,8 @@ static bool small_ok(int M, int N, int nslab, const void* p0, const void* p1, in
   return M <= 128 && N % 4 == 0 && nslab <= 8 && ((uintptr_t)p0 % 16 == 0) &&
          ((uintptr_t)p1 % 16 == 0) && (nslab == 1 || stride % 4 == 0);
 }
+// the small forms move a row's 4 dropout-mask bytes as one word (NULL counts as aligned, as in v4_*)
+static inline bool al4(const void* p) { return (uintptr_t)p % 4 == 0; }
 
 #define PKC_SMALL_LAUNCH_X(KERN, G, XM, args, M, nslab, stream)                                  \
   do {                                                                                         \
@@ -1007,7 +1024,8 @@ extern "C" int pkc_dense_fwd(const pkc_dense_fwd_args* a, float* work, void* str
                 "pkc_dense_fwd: slab_stride too small");
   if (small_ok(a->M, a->N, a->nslab, a->zslab, a->out ? a->out : a->zslab, a->slab_stride) &&
       (uintptr_t)a->xhat % 16 == 0 && (uintptr_t)a->out_bf16 % 8 == 0 && (!a->bias || (uintptr_t)a->bias % 16 == 0) &&
-      (a->norm == PKC_NORM_NONE || ((uintptr_t)a->gamma % 16 == 0 && (uintptr_t)a->beta % 16 == 0 &&
+      al4(a->keep_in) && al4(a->keep_out) &&
+      (a->norm == PKC_NORM_NONE ||((uintptr_t)a->gamma % 16 == 0 && (uintptr_t)a->beta % 16 == 0 &&
                                     (uintptr_t)a->running_mean % 16 == 0 &&
                                     (uintptr_t)a->running_var % 16 == 0)) &&
       (a->norm != PKC_NORM_BN_TRAIN ||
@@ -1070,6 +1088,7 @@ extern "C" int pkc_dense_bwd(const pkc_dense_bwd_args* a, float* work, void* str
                 "pkc_dense_bwd: dz_scratch needs dz_bf16 and training BatchNorm");
   if (small_ok(a->M, a->N, a->nslab, a->gslab, a->dz, a->slab_stride) &&
       (uintptr_t)a->xhat % 16 == 0 && (uintptr_t)a->dz_bf16 % 8 == 0 && (!a->dbias || (uintptr_t)a->dbias % 16 == 0) &&
+      al4(a->keep) &&
       (a->norm == PKC_NORM_NONE ||
        ((uintptr_t)a->gamma % 16 == 0 && (uintptr_t)a->beta % 16 == 0 &&
         (uintptr_t)a->save_invstd % 16 == 0 && (!a->dgamma || (uintptr_t)a->dgamma % 16 == 0) &&
