@@ -231,11 +231,23 @@ int pkc_dense_bwd_sync_apply(const pkc_dense_bwd_args* a, float* work, const flo
  * Fused LogSoftmax + NLLLoss(mean) + error rate + d(loss)/d(logits) for one output head
  * (neural_networks.py:73-74 LogSoftmax(dim=1); utils.py:1935-1952 NLLLoss; utils.py:1993-2011
  * cost_err; autograd backward softmax - onehot).  logits = sum_s zslab[s] + bias.
- * labels are read as float from a strided column (the reference stores them as float columns of
- * the chunk, core.py:94, cast with .long() at utils.py:1942).  Per-row loss/err go to row_loss /
- * row_err; dlogits = weight/M * (softmax - onehot) (NULL in forward-only mode); logp (M x N) is
- * the head output (NULL when not needed).  prior (N, log prior) is subtracted from logp when
+ * labels are int32, in [0, N), read from a strided column: labels[r * label_stride] (the
+ * reference stores them as float columns of the chunk, core.py:94, cast with .long() at
+ * utils.py:1942; here they arrive as integers).  labels == NULL is the forward mode: no dlogits,
+ * row_loss and row_err stay unwritten.  Per-row loss/err go to row_loss / row_err (each optional);
+ * row_loss is -log softmax at the label, before the prior; row_err is 1 when the first index of
+ * the row's maximum is not the label.  dlogits = weight/M * (softmax - onehot) (NULL: no
+ * backward; it needs labels).  logp (M x N) is the head output and is required: the form for
+ * wide or many-slab heads stages the logits in it.  log_prior (N) is subtracted from logp when
  * non-NULL (core.py:242-245 posterior normalisation).
+ * Forms, chosen by shape and alignment: register-resident for nslab <= 8 and N <= 511 (one wave
+ * per row) or 512 <= N <= 2048 (four waves per row), with 16-byte accesses when N % 4 == 0,
+ * slab_stride % 4 == 0 (nslab > 1), every fp32 pointer is 16-byte and dlogits_bf16 8-byte
+ * aligned, scalar accesses otherwise; one general form per width beyond that.
+ * pkc_nll_form (host only, no launch) names the form pkc_nll_fused takes for `a`: 8 * (16-byte
+ * accesses) + 4 * (four waves per row) + log2(slab capacity 1, 2, 4, 8) in 0..15 for the
+ * register-resident forms, -1 / -2 for the general form with one / four waves per row, -3 for
+ * arguments without a shape (M, N <= 0 or nslab < 1).
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
   int M, N, nslab;
@@ -247,6 +259,7 @@ typedef struct {
   void* dlogits_bf16;  /* optional bf16 copy of dlogits (operand of the fused row backward) */
 } pkc_nll_args;
 int pkc_nll_fused(const pkc_nll_args* a, void* stream);
+int pkc_nll_form(const pkc_nll_args* a);
 
 /* mse cost (utils.py:2045-2048: torch.mean((y - target) ** 2) over all M x N elements) and its
  * backward in one pass: row_loss[r] = (1/N) sum_j (y[r,j] - target[r,j])^2, so that mean_r row_loss

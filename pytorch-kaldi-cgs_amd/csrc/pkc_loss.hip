@@ -432,46 +432,57 @@ static bool nll_vec_ok(const pkc_nll_args* a) {
          al(a->log_prior, 16) && al(a->dlogits_bf16, 8);
 }
 
+// wide heads (4 waves per row) from 512 columns on
+static bool nll_wide(const pkc_nll_args* a) { return a->N >= 512; }
+
+// the register-resident forms: code = 8 * (16-byte form) + 4 * (wide) + log2(NS), nwg workgroups;
+// false for a head that takes nll_kernel (more than 8 slabs or more than 8 values per thread)
+static bool nll_reg_code(const pkc_nll_args* a, int* code, int* nwg) {
+  using namespace pkc;
+  const int ns = a->nslab <= 1 ? 0 : (a->nslab <= 2 ? 1 : (a->nslab <= 4 ? 2 : 3));
+  const bool wide = nll_wide(a);
+  if (a->nslab > 8 || a->N > (wide ? 2048 : 512)) return false;
+  *code = (nll_vec_ok(a) ? 8 : 0) + (wide ? 4 : 0) + ns;
+  *nwg = wide ? a->M : (a->M + LW - 1) / LW;
+  return true;
+}
+
+extern "C" int pkc_nll_form(const pkc_nll_args* a) {
+  if (!a || a->M <= 0 || a->N <= 0 || a->nslab < 1) return -3;
+  int code, nwg;
+  if (nll_reg_code(a, &code, &nwg)) return code;
+  return nll_wide(a) ? -2 : -1;
+}
+
 extern "C" int pkc_nll_fused(const pkc_nll_args* a, void* stream) {
   using namespace pkc;
   PKC_CHECK_ARG(a && a->M > 0 && a->N > 0 && a->nslab >= 1 && a->zslab && a->logp,
                 "pkc_nll_fused: bad arguments");
   PKC_CHECK_ARG(a->labels || !a->dlogits, "pkc_nll_fused: dlogits needs labels");
-  const int ns = a->nslab <= 1 ? 1 : (a->nslab <= 2 ? 2 : (a->nslab <= 4 ? 4 : 8));
-  const bool wide = a->N >= 512;
-  if (a->nslab <= 8 && a->N <= (wide ? 2048 : 512)) {
-    const dim3 grid(wide ? a->M : (a->M + LW - 1) / LW), blk(64 * LW);
+  int code, nwg;
+  if (nll_reg_code(a, &code, &nwg)) {
+    const dim3 grid(nwg), blk(64 * LW);
 #define PKC_NLL(K, W)                                                                 \
-    switch (ns) {                                                                     \
-      case 1: hipLaunchKernelGGL((K<W, 1>), grid, blk, 0, S(stream), *a); break;     \
-      case 2: hipLaunchKernelGGL((K<W, 2>), grid, blk, 0, S(stream), *a); break;     \
-      case 4: hipLaunchKernelGGL((K<W, 4>), grid, blk, 0, S(stream), *a); break;     \
+    switch (code & 3) {                                                               \
+      case 0: hipLaunchKernelGGL((K<W, 1>), grid, blk, 0, S(stream), *a); break;     \
+      case 1: hipLaunchKernelGGL((K<W, 2>), grid, blk, 0, S(stream), *a); break;     \
+      case 2: hipLaunchKernelGGL((K<W, 4>), grid, blk, 0, S(stream), *a); break;     \
       default: hipLaunchKernelGGL((K<W, 8>), grid, blk, 0, S(stream), *a); break;    \
     }
-    const bool v4 = nll_vec_ok(a);
-    if (wide) {
+    const bool v4 = (code & 8) != 0;
+    if (code & 4) {
       if (v4) { PKC_NLL(nll_vec_kernel, 4) } else { PKC_NLL(nll_reg_kernel, 4) }
     } else {
       if (v4) { PKC_NLL(nll_vec_kernel, 1) } else { PKC_NLL(nll_reg_kernel, 1) }
     }
 #undef PKC_NLL
-  } else if (wide) {
+  } else if (nll_wide(a)) {
     hipLaunchKernelGGL(nll_kernel<4>, dim3(a->M), dim3(64 * LW), 0, S(stream), *a);
   } else {
     hipLaunchKernelGGL(nll_kernel<1>, dim3((a->M + LW - 1) / LW), dim3(64 * LW), 0, S(stream), *a);
   }
   PKC_LAUNCH_CHECK("pkc_nll_fused");
   return PKC_OK;
-}
-
-static bool nll_reg_code(const pkc_nll_args* a, int* code, int* nwg) {
-  using namespace pkc;
-  const int ns = a->nslab <= 1 ? 0 : (a->nslab <= 2 ? 1 : (a->nslab <= 4 ? 2 : 3));
-  const bool wide = a->N >= 512;
-  if (a->nslab > 8 || a->N > (wide ? 2048 : 512)) return false;
-  *code = (nll_vec_ok(a) ? 8 : 0) + (wide ? 4 : 0) + ns;
-  *nwg = wide ? a->M : (a->M + LW - 1) / LW;
-  return true;
 }
 
 extern "C" int pkc_nll_fused_multi(const pkc_nll_args* args, int n, void* stream) {

@@ -215,6 +215,7 @@ _SIGS = {
     "pkc_dense_bwd_stats": (C.c_int, [C.POINTER(DenseBwdArgs), vp, vp, vp]),
     "pkc_dense_bwd_sync_apply": (C.c_int, [C.POINTER(DenseBwdArgs), vp, vp, C.c_int, vp]),
     "pkc_nll_fused": (C.c_int, [C.POINTER(NllArgs), vp]),
+    "pkc_nll_form": (C.c_int, [C.POINTER(NllArgs)]),
     "pkc_loss_finalize": (C.c_int, [C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
     "pkc_nll_fused_multi": (C.c_int, [vp, C.c_int, vp]),
     "pkc_logsoftmax_bwd": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp]),
