@@ -801,6 +801,55 @@ int pkc_sinc_ok(const pkc_sinc_args* a);
 int pkc_sinc_filters_fwd(const pkc_sinc_args* a, void* stream);
 int pkc_sinc_filters_bwd(const pkc_sinc_args* a, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Kaldi fbank / MFCC features from int16 audio (the `pkc-fbank` / `pkc-mfcc` fea_opts stages:
+ * compute-fbank-feats / compute-mfcc-feats with snip-edges, no dither, no VTLN, restated from
+ * Kaldi's published algorithm).  Additive to ABI 9.
+ *
+ * samples / utt_beg / utt_len: as pkc_wav_frames (the int16 audio of n_utts whole utterances).
+ * Output row r (of `rows`, any order) is frame f = frame_of_row[r] of utterance u = utt_of_row[r],
+ * the L samples from f * S; a row whose (u, f) names no whole frame (u outside 0..n_utts-1, f < 0
+ * or f * S + L > utt_len[u]) is left unwritten.  Per frame (x, y, E, m and out are float32; the
+ * FFT, p and every sum are carried in fp64):
+ *   1. x = the L samples;  remove_dc: x -= mean(x) (the sum is an exact integer sum)
+ *   2. raw_energy: E = log(max(sum x^2, FLT_EPSILON))
+ *   3. y[i] = x[i] - preemph * x[i-1] (i >= 1), y[0] = x[0] - preemph * x[0];  y *= window
+ *   4. !raw_energy: E = log(max(sum y^2, FLT_MIN))
+ *   5. y zero-padded to N, real FFT, p[k] = |Y[k]|^2 (use_power) or |Y[k]| for k < N/2
+ *   6. m[b] = log(max(sum_{i < mel_count[b]} mel_weight[mel_offset[b] + i] * p[mel_first[b] + i],
+ *                     FLT_EPSILON));  the Nyquist bin enters no band (mel_first + mel_count <= N/2)
+ *   7. fbank: out = [E if use_energy] m;  D = num_bins + use_energy
+ *      mfcc:  out[k] = lifter[k] * sum_n dct[k][n] * m[n], out[0] = E if use_energy;  D = num_ceps
+ *      where E = max(E, log_energy_floor) (pass -INFINITY for no floor).
+ * Host-built device tables (evaluated in double, stored as float): window (L); twiddle (N/2 pairs
+ * cos(2 pi k / N), -sin(2 pi k / N), kept as doubles); the mel bands as first bin / count / offset into mel_weight
+ * (num_bins each); dct (num_ceps x num_bins) and lifter (num_ceps), mfcc only.
+ * Every sum runs in a fixed order, there are no atomics and a row reads only its own samples:
+ * equal inputs give equal bits, and a row does not depend on the other rows of the call.
+ *
+ * pkc_kaldi_feats_ok: 1 when the shape is supported (else 0 and a pkc_last_error() text): N a
+ * power of two in 4..4096, 2 <= L <= N, S >= 1, 1 <= num_bins <= 256, D <= 256 and consistent with
+ * the kind, 1 <= num_ceps <= num_bins for mfcc.  pkc_kaldi_feats launches nothing for rows == 0.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  int L, S, N;                      /* frame length, frame shift (samples); FFT length */
+  int num_bins, num_ceps, D;
+  int mfcc;                         /* 0: fbank, 1: mfcc */
+  int use_energy, raw_energy, use_power, remove_dc;
+  float preemph, log_energy_floor;
+  int n_utts;
+  int64_t rows;
+  const int16_t* samples; const int64_t* utt_beg; const int32_t* utt_len;      /* (n_utts) */
+  const int32_t* utt_of_row; const int32_t* frame_of_row;                      /* (rows) */
+  const float* window; const double* twiddle;
+  const int32_t* mel_first; const int32_t* mel_count; const int32_t* mel_offset;
+  const float* mel_weight;
+  const float* dct; const float* lifter;
+  float* out;                       /* (rows, D) */
+} pkc_kaldi_feats_args;
+int pkc_kaldi_feats_ok(const pkc_kaldi_feats_args* a);
+int pkc_kaldi_feats(const pkc_kaldi_feats_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,17 @@ class SincArgs(C.Structure):
                 ("dW", vp), ("dlow", vp), ("dband", vp)]
 
 
+class KaldiFeatsArgs(C.Structure):
+    _fields_ = [("L", C.c_int), ("S", C.c_int), ("N", C.c_int), ("num_bins", C.c_int),
+                ("num_ceps", C.c_int), ("D", C.c_int), ("mfcc", C.c_int), ("use_energy", C.c_int),
+                ("raw_energy", C.c_int), ("use_power", C.c_int), ("remove_dc", C.c_int),
+                ("preemph", C.c_float), ("log_energy_floor", C.c_float), ("n_utts", C.c_int),
+                ("rows", i64), ("samples", vp), ("utt_beg", vp), ("utt_len", vp),
+                ("utt_of_row", vp), ("frame_of_row", vp), ("window", vp), ("twiddle", vp),
+                ("mel_first", vp), ("mel_count", vp), ("mel_offset", vp), ("mel_weight", vp),
+                ("dct", vp), ("lifter", vp), ("out", vp)]
+
+
 class RegItem(C.Structure):
     _fields_ = [("p", vp), ("g", vp), ("ld", i64), ("r0", C.c_int), ("r1", C.c_int),
                 ("c0", C.c_int), ("c1", C.c_int), ("block", C.c_int), ("assign", C.c_int)]
@@ -238,6 +249,8 @@ _SIGS = {
     "pkc_feat_frontend": (C.c_int, [vp, C.c_int, i64, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int,
                                     C.c_int, vp, vp]),
     "pkc_wav_frames": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "pkc_kaldi_feats_ok": (C.c_int, [C.POINTER(KaldiFeatsArgs)]),
+    "pkc_kaldi_feats": (C.c_int, [C.POINTER(KaldiFeatsArgs), vp]),
     "pkc_ark_write_mat": (C.c_int, [C.c_char_p, C.c_int, C.c_char_p, i64, i64, vp]),
     "pkc_ark_index": (i64, [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i64,
                             C.c_char_p, i64]),

@@ -69,7 +69,8 @@ def _read_features(fea_scp, fea_opts, output_folder):
     The scp's binary arks ("key path:offset" or "key path") are read directly.  An
     ``apply-cmvn ... | add-deltas ...`` fea_opts pipe (every shipped cfg) is parsed into a
     pkc.frontend.FeaFrontend that pkc_feat_frontend applies on the GPU after the upload; a
-    ``pkc-wav-frames`` stage makes fea_scp a wav list whose signals are framed on the GPU; any other
+    ``pkc-wav-frames`` stage makes fea_scp a wav list whose signals are framed on the GPU, a leading
+    ``pkc-fbank`` / ``pkc-mfcc`` stage one whose fbank / MFCC features are computed there; any other
     pipe is run through Kaldi exactly as the reference does.  Returns (feats, frontend or None)."""
     if fea_opts.strip() and not FE.is_native_pipe(fea_opts):
         import subprocess
@@ -81,6 +82,10 @@ def _read_features(fea_scp, fea_opts, output_folder):
         # pkc-wav-frames: fea_lst is the wav list save_raw_fea.py reads; the int16 signals go to
         # the GPU and pkc_wav_frames cuts the frames there (D.stage_chunk)
         return {k: frontend.wav.read(k, p) for k, p in FE.read_wav_list(fea_scp)}, frontend
+    if frontend is not None and frontend.feats is not None:
+        # pkc-fbank / pkc-mfcc: fea_lst is a wav list too; pkc_kaldi_feats computes the features
+        # from the int16 signals on the GPU, in front of the apply-cmvn / add-deltas launch
+        return {k: frontend.feats.read(k, p) for k, p in FE.read_wav_list(fea_scp)}, frontend
     feats = {}
     by_file = {}
     with open(fea_scp) as f:

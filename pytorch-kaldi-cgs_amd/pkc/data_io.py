@@ -320,17 +320,24 @@ class StagedChunk:
     sorted / split order on the same stream.
 
     With a wav-list stream (pkc.frontend.WavFrames) the upload is the utterances' int16 samples
-    and pkc_wav_frames cuts the (N, W) matrix of overlapping windows from them, on that stream."""
+    and pkc_wav_frames cuts the (N, W) matrix of overlapping windows from them, on that stream.
 
-    def __init__(self, names, raw, lab_arrays, end_index, device, fe_args=None, wav_args=None):
+    With a pkc-fbank / pkc-mfcc stream (pkc.frontend.KaldiFeats) the upload is the int16 samples
+    too; pkc_kaldi_feats computes the utterances' features and pkc_feat_frontend reads them."""
+
+    def __init__(self, names, raw, lab_arrays, end_index, device, fe_args=None, wav_args=None,
+                 kf_args=None):
         self.names, self.lab_arrays, self.end_index = names, lab_arrays, end_index
         dev = torch.device(device)
         self.stream = torch.cuda.Stream(device=dev)
         if wav_args is not None:
             pinned = wav_args["pinned"]
         else:
-            host = [raw] + ([] if fe_args is None else list(fe_args["arrays"]))
-            pinned = []
+            # kf_args (pkc.frontend.KaldiFeats): the frames of fe_args' raw are computed from the
+            # int16 audio by pkc_kaldi_feats on this stream, not uploaded
+            host = ([] if kf_args is not None else [raw]) + (
+                [] if fe_args is None else list(fe_args["arrays"]))
+            pinned = [] if kf_args is None else list(kf_args["pinned"])
             for a in host:
                 t = torch.empty(a.shape, dtype=torch.float32 if a.dtype == np.float32 else torch.int32,
                                 pin_memory=True)
@@ -344,10 +351,14 @@ class StagedChunk:
             elif fe_args is None:
                 self.raw_d = dev_t[0]
             else:
+                if kf_args is not None:
+                    nk = len(kf_args["pinned"])
+                    self._kf_inputs = dev_t[:nk]
+                    dev_t = [kaldi_feats_device(dev_t[:nk], kf_args["kf"], self.stream)] + dev_t[nk:]
                 raw_src, srow, urow, ubeg, uend, unorm, norm, scales = dev_t
                 Nout, Dout = fe_args["out_shape"]
                 self.raw_d = torch.empty(Nout, Dout, dtype=torch.float32, device=dev)
-                call("pkc_feat_frontend", ptr(raw_src), int(raw.shape[1]), Nout, ptr(srow),
+                call("pkc_feat_frontend", ptr(raw_src), int(fe_args["D"]), Nout, ptr(srow),
                      ptr(urow), ptr(ubeg), ptr(uend), ptr(unorm), ptr(norm), fe_args["cmvn_mode"],
                      ptr(scales), fe_args["order"], fe_args["maxoff"], ptr(self.raw_d),
                      C.c_void_p(self.stream.cuda_stream))
@@ -362,17 +373,25 @@ def frontend_args(fea, pieces, frontend):
     """Host tables of pkc_feat_frontend for these pieces: the utterances' raw frames in one array
     (each utterance whole, in order of first use), per-output-row source frame and utterance,
     per-utterance frame range and cmvn table index, the cmvn tables and the delta windows."""
+    keys = list(dict.fromkeys(k for k, _, _ in pieces))
+    D = fea[keys[0]].shape[1] if keys else 0
+    fa = frontend_maps({k: len(fea[k]) for k in keys}, D, pieces, frontend)
+    fa["raw"] = np.ascontiguousarray(np.concatenate([fea[k] for k in keys]), dtype=np.float32)
+    return fa
+
+
+def frontend_maps(n_frames, D, pieces, frontend):
+    """frontend_args without the frames themselves: n_frames {utt: frame count}, D their width.
+    `keys` names the utterances in the order their frames must lie in pkc_feat_frontend's raw."""
     from .frontend import delta_scales
     keys = list(dict.fromkeys(k for k, _, _ in pieces))
     if not keys:
         raise ValueError("empty chunk: no utterance survived the feature / label / cmvn filters")
-    D = fea[keys[0]].shape[1]
     uid = {k: i for i, k in enumerate(keys)}
-    lens = np.array([len(fea[k]) for k in keys], dtype=np.int64)
+    lens = np.array([n_frames[k] for k in keys], dtype=np.int64)
     ubeg = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
     if int(lens.sum()) >= 2 ** 31:
         raise ValueError("chunk too large for the int32 front-end row maps")
-    raw = np.ascontiguousarray(np.concatenate([fea[k] for k in keys]), dtype=np.float32)
     srow = np.concatenate([np.arange(a, b) + ubeg[uid[k]] for k, a, b in pieces]).astype(np.int32)
     urow = np.concatenate([np.full(b - a, uid[k]) for k, a, b in pieces]).astype(np.int32)
     kept, norm, nidx, mode = frontend.norm_tables(keys, D)
@@ -384,7 +403,7 @@ def frontend_args(fea, pieces, frontend):
     scales, maxoff = delta_scales(frontend.order, frontend.window)
     arrays = [srow, urow, ubeg.astype(np.int32), (ubeg + lens).astype(np.int32),
               nidx.astype(np.int32), norm.astype(np.float32), scales.astype(np.float32)]
-    return dict(raw=raw, arrays=arrays, cmvn_mode=mode, order=frontend.order, maxoff=maxoff,
+    return dict(keys=keys, D=D, arrays=arrays, cmvn_mode=mode, order=frontend.order, maxoff=maxoff,
                 out_shape=(len(srow), frontend.out_dim(D)))
 
 
@@ -442,7 +461,86 @@ def frame_signals(sig, wav, device="cuda"):
     return out
 
 
+def kaldi_feats_args(sig, keys, kf):
+    """Host tables of pkc_kaldi_feats for every frame of the utterances `keys`, whole utterance
+    after whole utterance (the `raw` layout of pkc_feat_frontend), in pinned memory.
+    sig: {utt: int16 samples}; kf: pkc.frontend.KaldiFeats."""
+    lens = np.array([len(sig[k]) for k in keys], dtype=np.int64)
+    nfr = [kf.n_frames(int(n)) for n in lens]
+    ubeg = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    if sum(nfr) >= 2 ** 31 or int(lens.max()) >= 2 ** 30:
+        raise ValueError("chunk too large for the int32 front-end row maps")
+    samples = torch.empty((int(lens.sum()),), dtype=torch.int16, pin_memory=True)
+    buf = samples.numpy()
+    for k, o in zip(keys, ubeg):
+        buf[o:o + len(sig[k])] = sig[k]
+    tab = kf.tables()
+    host = [ubeg, lens.astype(np.int32),
+            np.concatenate([np.full(n, u) for u, n in enumerate(nfr)]).astype(np.int32),
+            np.concatenate([np.arange(n) for n in nfr]).astype(np.int32),
+            tab["window"], tab["twiddle"], tab["mel_first"], tab["mel_count"], tab["mel_offset"],
+            tab["mel_weight"]]
+    if kf.kind == "mfcc":
+        host += [tab["dct"], tab["lifter"]]
+    pinned = [samples]
+    for a in host:
+        t = torch.empty(a.shape, dtype=torch.from_numpy(a[:0]).dtype, pin_memory=True)
+        t.numpy()[...] = a
+        pinned.append(t)
+    return dict(pinned=pinned, kf=kf, rows=int(sum(nfr)))
+
+
+def kaldi_feats_device(dev_t, kf, stream, out=None):
+    """pkc_kaldi_feats over the device copies of kaldi_feats_args' tables on `stream` (the current
+    one): the (rows, D) float32 matrix of whole utterances (written into `out` when given)."""
+    samples, ubeg, ulen, urow, frow, window, twiddle, mfirst, mcount, moff, mweight = dev_t[:11]
+    dct, lifter = dev_t[11:13] if kf.kind == "mfcc" else (None, None)
+    if out is None:
+        out = torch.empty(urow.numel(), kf.D, dtype=torch.float32, device=samples.device)
+    if out.shape != (urow.numel(), kf.D) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("kaldi_feats_device: out must be a contiguous (%d, %d) float32 matrix"
+                         % (urow.numel(), kf.D))
+    o = kf.opts
+    a = L.KaldiFeatsArgs(
+        L=kf.L, S=kf.S, N=kf.N, num_bins=kf.B, num_ceps=kf.C, D=kf.D, mfcc=int(kf.kind == "mfcc"),
+        use_energy=int(o["use-energy"]), raw_energy=int(o["raw-energy"]),
+        use_power=int(o["use-power"]), remove_dc=int(o["remove-dc-offset"]),
+        preemph=o["preemphasis-coefficient"], log_energy_floor=kf.log_energy_floor(),
+        n_utts=ubeg.numel(), rows=urow.numel(), samples=ptr(samples), utt_beg=ptr(ubeg),
+        utt_len=ptr(ulen), utt_of_row=ptr(urow), frame_of_row=ptr(frow), window=ptr(window),
+        twiddle=ptr(twiddle), mel_first=ptr(mfirst), mel_count=ptr(mcount), mel_offset=ptr(moff),
+        mel_weight=ptr(mweight), dct=ptr(dct), lifter=ptr(lifter), out=ptr(out))
+    if L.lib().pkc_kaldi_feats_ok(C.byref(a)) != 1:
+        raise NotImplementedError("%s not on the pkc path: %s"
+                                  % (kf.stage, L.lib().pkc_last_error().decode()))
+    call("pkc_kaldi_feats", C.byref(a), C.c_void_p(stream.cuda_stream))
+    return out
+
+
+def kaldi_features(sig, kf, device="cuda"):
+    """Every frame of every utterance of sig ({utt: int16 samples}, in its order; each with at
+    least one frame) on the current stream -> (rows, D) float32 device matrix."""
+    ka = kaldi_feats_args(sig, list(sig), kf)
+    dev_t = [t.to(device, non_blocking=True) for t in ka["pinned"]]
+    cur = torch.cuda.current_stream(dev_t[0].device)
+    out = kaldi_feats_device(dev_t, kf, cur)
+    cur.synchronize()                                          # the pinned tables die with ka
+    return out
+
+
 def stage_chunk(fea, labs, max_sequence_length, device="cuda", frontend=None):
+    if frontend is not None and frontend.feats is not None:
+        # fea: {utt: int16 samples} of a wav list; fbank / mfcc are computed on the GPU and the
+        # apply-cmvn / add-deltas launch reads them there.  Kaldi writes nothing for an utterance
+        # without a frame, apply-cmvn nothing for one without statistics
+        kf = frontend.feats
+        fea = {k: s for k, s in fea.items() if kf.n_frames(len(s)) > 0}
+        kept = set(frontend.norm_tables(sorted(fea), kf.D)[0])
+        lens = {k: kf.n_frames(len(s)) for k, s in fea.items() if k in kept}
+        names, pieces, lab_arrays, end_index = dataset_pieces(lens, labs, max_sequence_length)
+        fa = frontend_maps(lens, kf.D, pieces, frontend)
+        return StagedChunk(names, None, lab_arrays, end_index, device, fe_args=fa,
+                           kf_args=kaldi_feats_args(fea, fa["keys"], kf))
     if frontend is not None and frontend.wav is not None:
         # fea: {utt: (int16 samples, peak)} of a wav list; the frames are cut on the GPU
         wav = frontend.wav

@@ -18,6 +18,11 @@ against the independent C restatement in oracle/kaldi_feat.c.
 A pkc extension stands beside them: the one-stage pipe ``pkc-wav-frames ... ark:- ark:- |`` makes
 fea_lst a wav list and cuts the raw-waveform frames of the reference's save_raw_fea.py on the GPU
 (``WavFrames``, pkc_wav_frames in csrc/pkc_wav.hip); that one is pinned to the script's own output.
+
+``pkc-fbank`` / ``pkc-mfcc`` as the FIRST stage also make fea_lst a wav list: Kaldi's
+compute-fbank-feats / compute-mfcc-feats run on the GPU (``KaldiFeats``, pkc_kaldi_feats in
+csrc/pkc_kaldi_feats.hip) and feed the apply-cmvn / add-deltas stages behind them.  The log-mel
+values are pinned to transformers.audio_utils, a third-party Kaldi-compatible implementation.
 """
 import os
 import re
@@ -145,6 +150,23 @@ def delta_scales(order, window):
 WAV_STAGE = "pkc-wav-frames"
 
 
+def read_pcm16(stage, utt, path, fs, fs_opt):
+    """Mono 16-bit PCM wav sampled at fs (the standard library's `wave`) -> int16 samples; anything
+    else raises ValueError naming the utterance.  fs_opt: the stage's rate option, for the message."""
+    import wave
+    with wave.open(path, "rb") as w:
+        if w.getnchannels() != 1:
+            raise ValueError("%s: utterance %s: %d channels in %s (mono only)"
+                             % (stage, utt, w.getnchannels(), path))
+        if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
+            raise ValueError("%s: utterance %s: %d-byte samples in %s (16-bit PCM only)"
+                             % (stage, utt, w.getsampwidth(), path))
+        if w.getframerate() != fs:
+            raise ValueError("%s: utterance %s: %s is sampled at %d Hz, %s"
+                             % (stage, utt, path, w.getframerate(), fs_opt))
+        return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16)
+
+
 class WavFrames:
     """The ``pkc-wav-frames`` stage: the framing of the reference's save_raw_fea.py (:42-104) over
     a wav list, so that a `raw` stream is read from the audio itself and not from an ark holding
@@ -189,19 +211,7 @@ class WavFrames:
 
     def read(self, utt, path):
         """Mono 16-bit PCM wav -> (int16 samples, peak max|s| in 1..32768), checked."""
-        import wave
-        with wave.open(path, "rb") as w:
-            if w.getnchannels() != 1:
-                raise ValueError("%s: utterance %s: %d channels in %s (mono only)"
-                                 % (WAV_STAGE, utt, w.getnchannels(), path))
-            if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
-                raise ValueError("%s: utterance %s: %d-byte samples in %s (16-bit PCM only)"
-                                 % (WAV_STAGE, utt, w.getsampwidth(), path))
-            if w.getframerate() != self.fs:
-                raise ValueError("%s: utterance %s: %s is sampled at %d Hz, --fs=%d"
-                                 % (WAV_STAGE, utt, path, w.getframerate(), self.fs))
-            s = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16)
-        return self.signal(utt, s)
+        return self.signal(utt, read_pcm16(WAV_STAGE, utt, path, self.fs, "--fs=%d" % self.fs))
 
     def signal(self, utt, s):
         """(samples, peak) of an int16 signal after the checks of `check`; an all-zero signal is
@@ -212,6 +222,219 @@ class WavFrames:
         if peak == 0:
             raise ValueError("%s: utterance %s: the signal is all zero" % (WAV_STAGE, utt))
         return s, peak
+
+
+FEAT_STAGES = {"pkc-fbank": "fbank", "pkc-mfcc": "mfcc"}
+
+
+def _kaldi_bool(stage, opt, v):
+    s = str(v).strip().lower()
+    if s in ("true", "t", "1", ""):
+        return True
+    if s in ("false", "f", "0"):
+        return False
+    raise ValueError("%s: --%s=%s is not a boolean" % (stage, opt, v))
+
+
+class KaldiFeats:
+    """The ``pkc-fbank`` / ``pkc-mfcc`` stages: Kaldi's compute-fbank-feats / compute-mfcc-feats
+    over a wav list (feature-window.cc, mel-computations.cc, feature-fbank.cc, feature-mfcc.cc as
+    published), computed by pkc_kaldi_feats (csrc/pkc_kaldi_feats.hip) from the int16 audio.  The
+    options carry Kaldi's names and defaults, except --dither, which is 0 here (Kaldi: 1.0): a
+    random dither can be compared with nothing.  What the kernel does not compute is refused by
+    name with NotImplementedError, never approximated."""
+
+    FLOATS = {"sample-frequency": 16000.0, "frame-length": 25.0, "frame-shift": 10.0,
+              "preemphasis-coefficient": 0.97, "low-freq": 20.0, "high-freq": 0.0,
+              "energy-floor": 0.0, "cepstral-lifter": 22.0}
+    INTS = {"num-mel-bins": 23, "num-ceps": 13}
+    BOOLS = {"remove-dc-offset": True, "raw-energy": True, "use-power": True, "use-energy": None}
+    WINDOWS = ("povey", "hamming", "hanning", "rectangular")
+    MFCC_ONLY = ("num-ceps", "cepstral-lifter")
+    # option -> (the one value it may be given, as a parsed bool / float)
+    FIXED = {"dither": 0.0, "snip-edges": True, "htk-compat": False, "use-log-fbank": True,
+             "round-to-power-of-two": True}
+
+    def __init__(self, kind, **opts):
+        """kind: 'fbank' or 'mfcc'; opts: Kaldi's option names with '_' for '-', parsed values."""
+        if kind not in ("fbank", "mfcc"):
+            raise ValueError("KaldiFeats kind %r" % (kind,))
+        self.kind = kind
+        self.stage = "pkc-" + kind
+        o = dict(self.FLOATS)
+        o.update(self.INTS)
+        o.update(self.BOOLS)
+        o["window-type"] = "povey"
+        o["use-energy"] = kind == "mfcc"
+        for k, v in opts.items():
+            k = k.replace("_", "-")
+            if k not in o or (kind == "fbank" and k in self.MFCC_ONLY):
+                raise NotImplementedError("%s: option --%s" % (self.stage, k))
+            o[k] = v
+        self.opts = o
+        if o["window-type"] not in self.WINDOWS:
+            raise NotImplementedError("%s: --window-type=%s (povey, hamming, hanning and "
+                                      "rectangular are computed)" % (self.stage, o["window-type"]))
+        self.fs = o["sample-frequency"]
+        self.L = int(self.fs * 0.001 * o["frame-length"])
+        self.S = int(self.fs * 0.001 * o["frame-shift"])
+        if self.L < 2 or self.S < 1:
+            raise ValueError("%s: a frame of %d samples shifted by %d" % (self.stage, self.L, self.S))
+        self.N = 1
+        while self.N < self.L:
+            self.N *= 2
+        self.B = int(o["num-mel-bins"])
+        self.C = int(o["num-ceps"]) if kind == "mfcc" else 0
+        if self.B < 3:
+            raise ValueError("%s: --num-mel-bins=%d (Kaldi needs at least 3)" % (self.stage, self.B))
+        if kind == "mfcc" and not 1 <= self.C <= self.B:
+            raise ValueError("%s: --num-ceps=%d must be in 1..--num-mel-bins=%d"
+                             % (self.stage, self.C, self.B))
+        if not 0.0 <= o["preemphasis-coefficient"] <= 1.0:
+            raise ValueError("%s: --preemphasis-coefficient=%g" % (self.stage,
+                                                                   o["preemphasis-coefficient"]))
+        nyq = 0.5 * self.fs
+        self.high = o["high-freq"] if o["high-freq"] > 0.0 else nyq + o["high-freq"]
+        if not (0.0 <= o["low-freq"] < nyq and 0.0 < self.high <= nyq and o["low-freq"] < self.high):
+            raise ValueError("%s: bad --low-freq=%g / --high-freq=%g for a Nyquist of %g"
+                             % (self.stage, o["low-freq"], o["high-freq"], nyq))
+        self.D = self.C if kind == "mfcc" else self.B + int(o["use-energy"])
+        self._tables = None
+
+    @staticmethod
+    def read_conf(path):
+        """Kaldi conf file: one ``--opt=value`` per line, ``#`` starts a comment -> {opt: value}."""
+        kv = {}
+        with open(path) as f:
+            for n, line in enumerate(f, 1):
+                line = line.split("#", 1)[0].strip()
+                if not line:
+                    continue
+                if not line.startswith("--"):
+                    raise ValueError("%s:%d: expected --option=value, got %r" % (path, n, line))
+                k, _, v = line[2:].partition("=")
+                kv[k.strip().replace("_", "-")] = v.strip()
+        return kv
+
+    @classmethod
+    def from_options(cls, stage, kv):
+        """stage: a key of FEAT_STAGES; kv: {option name: value string} of the command line.  A
+        --config file is read first and the command line overrides it."""
+        kv = dict(kv)
+        if "config" in kv:
+            conf = cls.read_conf(kv.pop("config"))
+            if "config" in conf:
+                raise NotImplementedError("%s: --config inside a conf file" % stage)
+            kv = dict(conf, **kv)
+        opts = {}
+        for k, v in kv.items():
+            if k.startswith("vtln-"):
+                raise NotImplementedError("%s: --%s (VTLN is not computed)" % (stage, k))
+            if k in cls.FIXED:
+                want = cls.FIXED[k]
+                got = float(v) if isinstance(want, float) else _kaldi_bool(stage, k, v)
+                if got != want:
+                    raise NotImplementedError("%s: --%s=%s is not computed (only --%s=%s)"
+                                              % (stage, k, v, k, str(want).lower()))
+            elif k in cls.FLOATS:
+                opts[k] = float(v)
+            elif k in cls.INTS:
+                opts[k] = int(v)
+            elif k in cls.BOOLS:
+                opts[k] = _kaldi_bool(stage, k, v)
+            elif k == "window-type":
+                opts[k] = v
+            else:
+                raise NotImplementedError("%s: option --%s" % (stage, k))
+        return cls(FEAT_STAGES[stage], **opts)
+
+    def n_frames(self, n):
+        """Kaldi's snip-edges frame count of an n-sample signal."""
+        return 0 if n < self.L else 1 + (n - self.L) // self.S
+
+    def read(self, utt, path):
+        """Mono 16-bit PCM wav at --sample-frequency -> int16 samples on Kaldi's scale."""
+        return read_pcm16(self.stage, utt, path, self.fs, "--sample-frequency=%g" % self.fs)
+
+    def window(self):
+        a = 2.0 * np.pi / (self.L - 1)
+        i = np.arange(self.L, dtype=np.float64)
+        kind = self.opts["window-type"]
+        if kind == "povey":
+            return (0.5 - 0.5 * np.cos(a * i)) ** 0.85
+        if kind == "hamming":
+            return 0.54 - 0.46 * np.cos(a * i)
+        if kind == "hanning":
+            return 0.5 - 0.5 * np.cos(a * i)
+        return np.ones(self.L)
+
+    def mel_bands(self):
+        """MelBanks::MelBanks: [(first FFT bin, float64 weights)] per band; the band edges are
+        equally spaced in mel, the triangles are linear in mel, both edge tests are strict, and
+        only bins below N/2 are looked at."""
+        def mel(f):
+            return 1127.0 * np.log(1.0 + f / 700.0)
+        ml, mh = mel(self.opts["low-freq"]), mel(self.high)
+        delta = (mh - ml) / (self.B + 1)
+        m = mel(self.fs / self.N * np.arange(self.N // 2, dtype=np.float64))
+        bands = []
+        for b in range(self.B):
+            left, center, right = ml + b * delta, ml + (b + 1) * delta, ml + (b + 2) * delta
+            idx = np.flatnonzero((m > left) & (m < right))
+            if len(idx) == 0:
+                raise ValueError("%s: mel band %d of %d is empty: --num-mel-bins is too large for "
+                                 "an FFT of %d" % (self.stage, b, self.B, self.N))
+            mm = m[idx[0]:idx[-1] + 1]
+            bands.append((int(idx[0]), np.where(mm <= center, (mm - left) / (center - left),
+                                                (right - mm) / (right - center))))
+        return bands
+
+    def dct_lifter(self):
+        """ComputeDctMatrix rows 0..C-1 and ComputeLifterCoeffs, in float64."""
+        n = np.arange(self.B, dtype=np.float64)
+        M = np.sqrt(2.0 / self.B) * np.cos(np.pi / self.B * (n[None, :] + 0.5)
+                                           * np.arange(self.C)[:, None])
+        M[0] = np.sqrt(1.0 / self.B)
+        Q = self.opts["cepstral-lifter"]
+        lift = np.ones(self.C) if Q == 0.0 else 1.0 + 0.5 * Q * np.sin(np.pi * np.arange(self.C) / Q)
+        return M, lift
+
+    def tables(self):
+        """The host-built tables of pkc_kaldi_feats, evaluated in float64 and stored as float32
+        (the FFT twiddles stay float64):
+        dict(window, twiddle, mel_first, mel_count, mel_offset, mel_weight[, dct, lifter])."""
+        if self._tables is None:
+            k = np.arange(self.N // 2, dtype=np.float64)
+            ang = 2.0 * np.pi * k / self.N
+            bands = self.mel_bands()
+            cnt = np.array([len(w) for _, w in bands], np.int32)
+            t = dict(window=self.window().astype(np.float32),
+                     twiddle=np.stack([np.cos(ang), -np.sin(ang)], 1),
+                     mel_first=np.array([f for f, _ in bands], np.int32), mel_count=cnt,
+                     mel_offset=np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int32),
+                     mel_weight=np.concatenate([w for _, w in bands]).astype(np.float32))
+            if self.kind == "mfcc":
+                dct, lift = self.dct_lifter()
+                t.update(dct=np.ascontiguousarray(dct, dtype=np.float32),
+                         lifter=lift.astype(np.float32))
+            self._tables = t
+        return self._tables
+
+    def log_energy_floor(self):
+        ef = self.opts["energy-floor"]
+        return float(np.log(ef)) if ef > 0.0 else float("-inf")
+
+
+def cmvn_stats(feats):
+    """compute-cmvn-stats of float32 feature matrices: the (2, D+1) float64 matrix whose row 0 is
+    [sum x, frame count] and row 1 [sum x^2, 0], accumulated in float64."""
+    m = np.concatenate([np.asarray(f, dtype=np.float64) for f in feats])
+    D = m.shape[1]
+    st = np.zeros((2, D + 1), np.float64)
+    st[0, :D] = m.sum(0)
+    st[1, :D] = (m * m).sum(0)
+    st[0, D] = len(m)
+    return st
 
 
 def read_wav_list(path):
@@ -226,18 +449,21 @@ def read_wav_list(path):
 
 
 class FeaFrontend:
-    """apply-cmvn / add-deltas stages of one fea_opts pipe, or its one pkc-wav-frames stage."""
+    """apply-cmvn / add-deltas stages of one fea_opts pipe, behind an optional first pkc-fbank /
+    pkc-mfcc stage, or its one pkc-wav-frames stage."""
 
     def __init__(self):
         self.cmvn = None          # dict(stats={key: (2, D+1) f64}, utt2spk={utt: spk} | None, vars)
         self.order, self.window = 0, 2
         self.wav = None           # WavFrames: fea_lst is a wav list
+        self.feats = None         # KaldiFeats: fea_lst is a wav list, fbank / mfcc computed first
 
     @staticmethod
     def parse(fea_opts):
         """fea_opts -> FeaFrontend (None for an empty pipe).  Stages other than apply-cmvn and
         add-deltas (and options Kaldi does not have) raise NotImplementedError; so does
-        pkc-wav-frames beside any other stage or with an option it does not have."""
+        pkc-wav-frames beside any other stage or with an option it does not have, and pkc-fbank /
+        pkc-mfcc anywhere but in front."""
         fe = FeaFrontend()
         stages = [s.strip() for s in fea_opts.split("|") if s.strip()]
         if not stages:
@@ -245,6 +471,9 @@ class FeaFrontend:
         if len(stages) > 1 and any(s.split()[0] == WAV_STAGE for s in stages):
             raise NotImplementedError("fea_opts: %s frames a wav list and must be the only stage of "
                                       "the pipe (got %s)" % (WAV_STAGE, " | ".join(stages)))
+        if any(s.split()[0] in FEAT_STAGES for s in stages[1:]):
+            raise NotImplementedError("fea_opts: pkc-fbank / pkc-mfcc read the wav list and must "
+                                      "be the first stage of the pipe (got %s)" % " | ".join(stages))
         for st in stages:
             argv = shlex.split(st)
             prog, args = argv[0], argv[1:]
@@ -262,6 +491,10 @@ class FeaFrontend:
                     raise NotImplementedError("%s %s: expected ark:- ark:-"
                                               % (WAV_STAGE, " ".join(pos)))
                 fe.wav = WavFrames(**{k.replace("-", "_"): int(v) for k, v in kv.items()})
+            elif prog in FEAT_STAGES:
+                if pos != ["ark:-", "ark:-"]:
+                    raise NotImplementedError("%s %s: expected ark:- ark:-" % (prog, " ".join(pos)))
+                fe.feats = KaldiFeats.from_options(prog, kv)
             elif prog == "apply-cmvn":
                 if fe.cmvn is not None or fe.order:
                     raise NotImplementedError("fea_opts: apply-cmvn after add-deltas / twice")
@@ -328,7 +561,7 @@ def kaldi_on_path():
                for d in os.environ.get("PATH", "").split(os.pathsep) if d)
 
 
-_PIPE_RE = re.compile(r"^\s*(apply-cmvn|add-deltas|pkc-wav-frames)\b")
+_PIPE_RE = re.compile(r"^\s*(apply-cmvn|add-deltas|pkc-wav-frames|pkc-fbank|pkc-mfcc)\b")
 
 
 def is_native_pipe(fea_opts):
