@@ -29,8 +29,9 @@ from . import dist as DP
 from . import frontend as FE
 from . import _lib as L
 from . import neural_networks as NN
-from .engine import Engine, ForwardRunner, parse_model
+from .engine import Engine, parse_model
 from .neural_networks import strtobool
+from .runners import ForwardRunner
 
 
 def _cfg_item2sec(config, field, value):

@@ -17,21 +17,28 @@ Design (MI355X-first):
   * matmuls: pkc_gemm (MFMA, split-K slabs summed by the consumers); BN/act/dropout fused in
     pkc_dense_fwd/_bwd; LogSoftmax+NLL+err+dlogits fused in pkc_nll_fused; every optimizer of
     every architecture in one pkc_optim_step that also re-applies HCGS masks.
+
+Layout: here the step (Engine), its launch operation (Op), every kernel-form switch (the constants
+below) and every function that reads one when called — tests flip a form by assigning the constant
+on THIS module, so none is copied elsewhere.  The graph vocabulary is pkc.graph, re-exported here;
+pkc.runners (forward mode) imports this module, never the other way round.
 """
 import ctypes as C
 import os
 import random
-import re
 import zlib
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib as L
 from ._lib import call, ptr
-from .cgs import kmeans_patterns
+# the graph vocabulary lives in pkc.graph; re-exported here, where its users import it from
+from .graph import (TENSOR_OPS, CombineNode, ConvNode, Layer, MseTerm, Node, NormLayer,  # noqa: F401
+                    RecNode, RegTerm, SeqBatch, StdRecNode, _b, _f32, conv_args, conv_post_args,
+                    parse_model, pattern_effective_masks, resolve_concat, sinc_args, sinc_bind)
 
-_PAT = re.compile(r"(.*)=(.*)\((.*),(.*)\)")
 # split-K slab budget of a layer output (<= 8: the small-batch dense kernels sum them in
 # registers); on the C2 step 4 gives 0.197 ms per step, 8 and 5 0.201, 3 0.211, 2 0.233
 MAX_SPLITS = int(os.environ.get("PKC_MAX_SPLITS", "4"))
@@ -118,104 +125,6 @@ FUSED_FWD = os.environ.get("PKC_FUSED_FWD", "0") != "0"
 REC_DY_PRESUM = os.environ.get("PKC_REC_DY_PRESUM", "1") != "0"
 
 
-_PAT3 = re.compile(r"(.*)=(.*)\((.*),(.*),(.*)\)")
-
-
-def parse_model(text):
-    """utils.py:1888-1903 line grammar: out=op(in1,in2), split at the LAST comma (greedy); a line
-    whose output name starts with 'loss_gl' is re-read as out=op(in1,in2,in3) (1904-1906), and
-    in3 rides in in2 as "in2,in3"."""
-    rows = []
-    for line in text.split("\n"):
-        if not line.strip():
-            continue
-        row = list(_PAT.findall(line)[0])
-        if row[0][:7] == "loss_gl":
-            o, op, a, b, c = _PAT3.findall(line)[0]
-            row = [o, op, a, b + "," + c]
-        rows.append(row)
-    return rows
-
-
-class RegTerm:
-    """One cost_l1 / cost_l2 / cost_gl line of the [model] (utils.py:24-60): a pseudo loss head
-    whose per-row 'loss' is the regulariser value (pkc_reg_finalize broadcasts it)."""
-    head = False
-
-    def __init__(self, op, lam, nblk, params):
-        self.op, self.lam, self.nblk, self.params = op, float(lam), nblk, params
-        self.kind = L.REG_L1 if op == "cost_l1" else L.REG_L2
-        self.loss_weight = 0.0
-
-    def items(self, grads):
-        """Row-slice items of every block, blocks in parameter order (gl: the torch.chunk grid
-        along dim 1, then dim 0 — utils.py:49-54)."""
-        items, bstart = [], [0]
-        for p in self.params:
-            R, Cc = p.shape[0], int(np.prod(p.shape[1:]))
-            if self.op == "cost_gl":
-                cs, rs = -(-Cc // self.nblk), -(-R // self.nblk)
-                cgrid = [(c, min(c + cs, Cc)) for c in range(0, Cc, cs)]
-                rgrid = [(r, min(r + rs, R)) for r in range(0, R, rs)]
-                rects = [(r0, r1, c0, c1) for c0, c1 in cgrid for r0, r1 in rgrid]
-            else:
-                rects = [(0, R, 0, Cc)]
-            g = grads.get(id(p))
-            for r0, r1, c0, c1 in rects:
-                per = max(1, 4096 // max(1, c1 - c0))
-                for a in range(r0, r1, per):
-                    items.append((p, g, Cc, a, min(a + per, r1), c0, c1, len(bstart) - 1))
-                bstart.append(len(items))
-        return items, bstart
-
-
-class MseTerm:
-    """One mse line of the [model] (utils.py:2045-2048: torch.mean((a - b) ** 2)) between a
-    feed-forward node's output and a feature stream of the chunk: a loss term whose per-row loss
-    is the row's mean square (pkc_mse_fused), and one more gradient source of its node."""
-    head = False
-
-    def __init__(self, node, c0, name):
-        self.node, self.c0, self.name = node, c0, name
-        self.loss_weight = 0.0
-
-
-def resolve_concat(lines, fea_cols):
-    """[model] concatenate(a, b) (utils.py:2014-2016: torch.cat along the feature axis) of feature
-    streams — or of earlier such concatenations — whose column ranges are adjacent in the chunk
-    matrix: read_lab_fea stacks the streams in fea_dict order (data_io.py:235-240), which is the
-    order the [model] first names them, so the result is the column range spanning both, a
-    zero-copy view of the chunk.  Returns fea_cols with those names added; every other
-    concatenate (a produced output on either side, streams that are not adjacent) is left to the
-    graph, where it becomes a CombineNode."""
-    cols = dict(fea_cols)
-    for out, op, a, b in lines:
-        if op != "concatenate":
-            continue
-        if a in cols and b in cols and cols[a][1] == cols[b][0]:
-            cols[out] = (cols[a][0], cols[b][1])
-        # (any other concatenate is a CombineNode of the graph, Engine._build_graph)
-    return cols
-
-
-class SeqBatch(tuple):
-    """(begin rows, lengths, left pads, T) of one sentence batch, plus .index: the batch's
-    position in the bound chunk (its data-parallel frame weight, Engine.frame_scales)."""
-
-    def __new__(cls, items, index):
-        t = tuple.__new__(cls, items)
-        t.index = index
-        return t
-
-
-def _f32(n, dev):
-    return torch.zeros(int(max(1, n)), dtype=torch.float32, device=dev)
-
-
-def _b(v):
-    return str(v).strip().lower() in ("1", "true", "yes", "y", "on", "t")
-
-
 def persist_geometry():
     """(waves, forward slots, BPTT slots, rows per workgroup, largest H) of the persistent loops."""
     v = [C.c_int() for _ in range(5)]
@@ -270,50 +179,6 @@ def _splits(M, N, K, cap):
     return max(1, min(cap, L.lib().pkc_gemm_pick_splits(M, N, K)))
 
 
-class Layer:
-    """One dense layer of an MLP architecture inside the graph."""
-    rec = False
-
-    def __init__(self, arch, idx, spec, K):
-        self.arch, self.idx, self.K = arch, idx, K
-        self.N = spec["out"]
-        self.spec = spec
-        self.act = spec["act"]
-        self.head = self.act == "softmax"
-        self.bn = spec["bn"]
-        self.drop = float(spec["drop"])
-        self.W, self.b = spec["W"], spec["b"]
-        self.gamma, self.beta, self.rm, self.rv = spec["gamma"], spec["beta"], spec["rm"], spec["rv"]
-        self.mask = spec["mask"]
-        self.src = None          # ("fea", c0, c1) or ("node", producer)
-        self.consumers = []
-        self.label_col = None
-        self.nbt0 = int(spec["nbt"].item()) if spec.get("nbt") is not None else 0
-        self.loss_weight = 0.0
-        self.name = "%s.%d" % (arch, idx)
-        if self.head and self.bn:
-            raise NotImplementedError("%s: BatchNorm before LogSoftmax is not on the pkc path" % self.name)
-        self.ln = bool(spec["ln"])                # LayerNorm between the Linear and BN / act
-        self.ln_gamma, self.ln_beta = spec.get("ln_gamma"), spec.get("ln_beta")
-        if self.act not in L.ACT and not self.head:
-            raise NotImplementedError("%s: activation %s" % (self.name, self.act))
-        self.qbits = int(spec["quant"] or 0)      # QuantizeLinear weight bits (0: nn.Linear)
-        self.ibits = int(spec["inp_quant"] or 0)  # QuantizeLinear input bits (0: off)
-        self.reads = 1 if self.ibits else 0       # in-place input quantisations this layer applies
-        self.Wq = None
-
-    def params(self):
-        out = [(self.W, "dW", self.mask), (self.b, "db", None)]
-        if self.ln:
-            out += [(self.ln_gamma, "dgamma_ln", None), (self.ln_beta, "dbeta_ln", None)]
-        if self.bn:
-            out += [(self.gamma, "dgamma", None), (self.beta, "dbeta", None)]
-        return out
-
-    def quant_of(self, p):
-        return (self.Wq, self.qbits) if (p is self.W and self.qbits) else (None, 0)
-
-
 # Block-sparse U in the recurrent step kernels for static HCGS masks: "auto" (when it cuts the
 # contraction), "force" (whenever the tiles fit, used by the parity tests) or "off".
 RNN_SPARSE = os.environ.get("PKC_RNN_SPARSE", "auto")
@@ -349,375 +214,18 @@ def ktile_table(mask, transpose, dev):
     return tab.to(dev), kmax, frac
 
 
-class NormLayer(Layer):
-    """An MLP's input LayerNorm / BatchNorm (dnn_use_laynorm_inp / dnn_use_batchnorm_inp,
-    neural_networks.py:246-251): a node with no matmul, normalising the arch's input."""
+class Op(NamedTuple):
+    """One operation of a launch of Engine._gemms: a matmul, or a gather / loss / column-sum /
+    slab-sum / optimizer operation beside it.  Labels are observable (profile_step, skip_labels)."""
+    label: str
+    flops: float
+    nbytes: float
+    prob: L.GemmProblem
+    half: Optional[Tuple[float, L.GemmProblem]] = None   # (bytes, problem) on bf16 operand copies
 
-    def __init__(self, arch, idx, spec, K):
-        self.arch, self.idx, self.K, self.N = arch, idx, K, K
-        self.spec = spec
-        self.kind = spec["kind"]
-        self.act, self.head, self.drop = "linear", False, 0.0
-        self.bn, self.ln = self.kind == "bn", self.kind == "ln"
-        self.gamma, self.beta = spec["gamma"], spec["beta"]
-        self.ln_gamma, self.ln_beta = spec["gamma"], spec["beta"]
-        self.rm, self.rv = spec.get("rm"), spec.get("rv")
-        self.W = self.b = self.mask = None
-        self.src, self.consumers, self.label_col = None, [], None
-        self.nbt0 = int(spec["nbt"].item()) if spec.get("nbt") is not None else 0
-        self.loss_weight = 0.0
-        self.name = "%s.inp_%s%d" % (arch, self.kind, idx)
-        self.qbits = self.ibits = self.reads = 0
-        self.Wq = None
-
-    def params(self):
-        if self.ln:
-            return [(self.gamma, "dgamma_ln", None), (self.beta, "dbeta_ln", None)]
-        return [(self.gamma, "dgamma", None), (self.beta, "dbeta", None)]
-
-
-TENSOR_OPS = ("concatenate", "mult", "sum", "avg", "sum_constant", "mult_constant")
-
-
-class CombineNode:
-    """One [model] tensor operation on produced outputs (utils.py:2014-2043: concatenate, mult,
-    sum, mult_constant, sum_constant, avg) as a graph node.  For its neighbours it is a node with
-    no matmul and no parameters (W is None, like an input norm): N, out (rows, N), its consumers'
-    dX slabs (or a recurrent consumer's layer-0 dX slabs) as its output gradient.  It has two
-    sources, each ("node", P) or ("fea", c0, c1) — one for the constant forms, whose second
-    operand is the float `c` — and writes each producer's gradient into ONE slab of that
-    producer's gradient slabs (cons_idx: its positions in the producers' consumer lists)."""
-    rec = False
-    combine = True
-    head = False
-    W = b = mask = Wq = None
-    qbits = ibits = reads = 0
-    bn = ln = False
-    act, drop = "linear", 0.0
-    arch = None
-
-    def __init__(self, out, op, srcs, widths, c=0.0):
-        self.op, self.srcs, self.c = op, srcs, float(c)
-        self.name = "%s=%s" % (out, op)
-        self.Na, self.Nb = widths[0], (widths[1] if len(widths) > 1 else 0)
-        if op not in ("concatenate", "sum_constant", "mult_constant") and self.Na != self.Nb:
-            raise NotImplementedError("%s: operands %d and %d wide (only concatenate takes "
-                                      "unequal widths)" % (self.name, self.Na, self.Nb))
-        self.N = self.Na + self.Nb if op == "concatenate" else self.Na
-        self.K = self.N
-        self.consumers, self.cons_idx = [], []
-        self.label_col, self.loss_weight = None, 0.0
-        self.heads_in = any(s[0] == "node" and s[1].head for s in srcs)
-
-    def params(self):
-        return []
-
-    def quant_of(self, p):
-        return (None, 0)
-
-
-class ConvNode:
-    """One Conv1d + max-pool layer of a CNN / SincNet architecture (neural_networks.py:2017-2029,
-    :2127-2139) as a graph node.  For its neighbours it is a dense node with no matmul of the
-    engine's own (W is None): N = C_out * L_out, out (rows, N) channel-major, consumers' dX slabs
-    (or a recurrent consumer's) as its output gradient, dX into its producer's slab.  The
-    convolution products are exact fp32 in every pkc_prec mode.  A sinc layer (SincNet's layer 0)
-    convolves with an engine-owned filter buffer regenerated from low_hz_ / band_hz_ at the start
-    of every forward; those two are its parameters, its dW a work buffer."""
-    rec = False
-    conv = True
-    head = False
-    W = b = mask = Wq = None          # no engine matmul, mask or quantised copy
-    qbits = ibits = reads = 0
-
-    def __init__(self, arch, idx, spec, K):
-        self.arch, self.idx, self.spec = arch, idx, spec
-        self.C_in, self.C_out, self.L_in, self.L_out = (spec["C_in"], spec["C_out"], spec["L_in"],
-                                                        spec["L_out"])
-        self.len, self.pool = spec["len"], spec["pool"]
-        if K != self.C_in * self.L_in:
-            raise ValueError("%s.conv%d: input width %d != C_in * L_in = %d"
-                             % (arch, idx, K, self.C_in * self.L_in))
-        self.K, self.N = K, self.C_out * self.L_out
-        self.name = "%s.conv%d" % (arch, idx)
-        self.act, self.drop = spec["act"], float(spec["drop"])
-        self.bn, self.ln = bool(spec["bn"]), bool(spec["ln"])
-        if self.bn and self.ln:
-            raise NotImplementedError("%s: LayerNorm and BatchNorm both set (the reference then "
-                                      "convolves twice, neural_networks.py:2019-2025)" % self.name)
-        if self.act not in L.ACT:
-            raise NotImplementedError("%s: activation %s on a convolution layer" % (self.name, self.act))
-        self.sinc = spec.get("sinc")
-        if self.sinc is not None:
-            sinc_bind(spec)
-        self.cW, self.cb = spec["W"], spec["b"]
-        self.gamma, self.beta, self.rm, self.rv = spec["gamma"], spec["beta"], spec["rm"], spec["rv"]
-        self.ln_gamma, self.ln_beta = spec["ln_gamma"], spec["ln_beta"]
-        self.src, self.consumers, self.label_col = None, [], None
-        self.nbt0 = int(spec["nbt"].item()) if spec.get("nbt") is not None else 0
-        self.loss_weight = 0.0
-
-    def params(self):
-        if self.sinc is not None:
-            out = [(self.sinc["low"], "dlow", None), (self.sinc["band"], "dband", None)]
-        else:
-            out = [(self.cW, "dW", None), (self.cb, "db", None)]
-        if self.ln:
-            out += [(self.ln_gamma, "dgamma_ln", None), (self.ln_beta, "dbeta_ln", None)]
-        if self.bn:
-            out += [(self.gamma, "dgamma", None), (self.beta, "dbeta", None)]
-        return out
-
-    def quant_of(self, p):
-        return (None, 0)
-
-
-def conv_args(sp, rows, x_ptr, ldx, z, off):
-    """pkc_conv1d_args of a conv_specs() entry over `rows` samples."""
-    a = L.Conv1dArgs(B=rows, C_in=sp["C_in"], L_in=sp["L_in"], C_out=sp["C_out"], len=sp["len"],
-                     pool=sp["pool"], x=x_ptr, ldx=ldx, W=sp["W"].data_ptr(),
-                     bias=sp["b"].data_ptr(), z=z.data_ptr(), off=off.data_ptr())
-    if L.lib().pkc_conv1d_ok(C.byref(a)) != 1:
-        raise NotImplementedError("convolution shape not on the pkc path: %s"
-                                  % L.lib().pkc_last_error().decode())
-    return a
-
-
-def sinc_bind(sp):
-    """Buffers of a sinc layer's conv_specs() entry: the generated filters as its W, a zero bias
-    (SincConv has none), the maximum and its index per filter, n_ and window_ on the device."""
-    sn = sp["sinc"]
-    dev, N, K = sn["low"].device, sp["C_out"], sp["len"]
-    sp["W"], sp["b"] = _f32(N * K, dev).view(N, 1, K), _f32(N, dev)
-    sn["max_"], sn["idx"] = _f32(N, dev), torch.zeros(N, dtype=torch.int32, device=dev)
-    sn["n_dev"] = sn["n_"].detach().reshape(-1).to(dev, torch.float32).contiguous()
-    sn["window_dev"] = sn["window"].detach().reshape(-1).to(dev, torch.float32).contiguous()
-    sinc_args(sp)
-
-
-def sinc_args(sp, **kw):
-    """pkc_sinc_args of a bound sinc layer."""
-    sn = sp["sinc"]
-    a = L.SincArgs(N=sp["C_out"], K=sp["len"], low_hz=sn["low"].data_ptr(),
-                   band_hz=sn["band"].data_ptr(), n_=sn["n_dev"].data_ptr(),
-                   window=sn["window_dev"].data_ptr(), sr=sn["sr"], min_low_hz=sn["min_low_hz"],
-                   min_band_hz=sn["min_band_hz"], filters=sp["W"].data_ptr(),
-                   max_=sn["max_"].data_ptr(), max_idx=sn["idx"].data_ptr(), **kw)
-    if (sn["n_dev"].numel() != a.K or sn["window_dev"].numel() != a.K
-            or L.lib().pkc_sinc_ok(C.byref(a)) != 1):
-        raise NotImplementedError("sinc filter bank not on the pkc path: %s"
-                                  % L.lib().pkc_last_error().decode())
-    return a
-
-
-def conv_post_args(sp, rows, z, train, out, **kw):
-    """pkc_conv_post_args of a conv_specs() entry (norm / activation / dropout after the pool)."""
-    if sp["ln"]:
-        norm, g, b, eps = L.CONV_NORM_LN, sp["ln_gamma"], sp["ln_beta"], sp.get("ln_eps", 1e-6)
-    elif sp["bn"]:
-        # eps = L_out: neural_networks.py:1988-1990 passes it as BatchNorm1d's second argument
-        norm, g, b, eps = (L.NORM_BN_TRAIN if train else L.NORM_BN_EVAL, sp["gamma"], sp["beta"],
-                           sp["bn_eps"])
-    else:
-        norm, g, b, eps = L.NORM_NONE, None, None, 0.0
-    return L.ConvPostArgs(B=rows, C=sp["C_out"], L=sp["L_out"], norm=norm, z=z.data_ptr(),
-                          gamma=ptr(g), beta=ptr(b), running_mean=sp["rm"].data_ptr(),
-                          running_var=sp["rv"].data_ptr(), momentum=sp.get("bn_momentum", 0.05),
-                          eps=eps, act=L.ACT[sp["act"]], out=out.data_ptr(), **kw)
-
-
-class RecNode:
-    """A whole liGRU / LSTM architecture (all its layers) as one graph node."""
-    rec = True
-    head = False
-
-    def __init__(self, arch, net, K):
-        self.arch, self.net, self.K = arch, net, K
-        self.name = arch
-        self.cell = {"lstm": L.CELL_LSTM, "gru": L.CELL_GRU, "ligru": L.CELL_LIGRU,
-                     "minimalgru": L.CELL_MINGRU, "rnn": L.CELL_RNN}[net.cell]
-        self.G = {L.CELL_LSTM: 4, L.CELL_GRU: 3, L.CELL_LIGRU: 2, L.CELL_MINGRU: 2,
-                  L.CELL_RNN: 1}[self.cell]
-        # two-phase cells: the candidate gate's U multiplies r*h (GRU) / z*h (minimalGRU)
-        self.cand = {L.CELL_GRU: 2, L.CELL_MINGRU: 1}.get(self.cell)
-        self.layers = net.layer_specs()
-        self.N = net.out_dim
-        self.src = None
-        self.consumers = []
-        self.loss_weight = 0.0
-        self.label_col = None
-        for sp in self.layers:
-            if sp["act"] not in L.ACT:
-                raise NotImplementedError("%s: activation %s" % (arch, sp["act"]))
-            sp["nbt0"] = [int(bn.num_batches_tracked.item()) for bn in sp["bnm"]]
-            sp.setdefault("qbits", 0)
-            sp.setdefault("ibits", 0)
-            if sp["ibits"] and sp["bidir"]:
-                raise NotImplementedError("%s: input quantisation of a bidirectional layer" % arch)
-        # in-place quantisations of the node's input (gate linears of layer 0)
-        self.ibits = self.layers[0]["ibits"]
-        self.reads = self.G if self.ibits else 0
-        self.qw = {}            # id(param) -> fake-quantised copy
-        self.emask = {}         # id(param) -> effective (HCGS x pattern) mask
-
-    def params(self):
-        out = []
-        for li, sp in enumerate(self.layers):
-            for g in range(self.G):
-                W = sp["W"][g]
-                wm = sp["Wmasks"][g] if sp.get("Wmasks") else sp["Wmask"]
-                out.append((W, ("dW", li, g), self.emask.get(id(W), wm)))
-                if sp["b"][g] is not None:
-                    out.append((sp["b"][g], ("db", li, g), None))
-            for g in range(self.G):
-                U = sp["U"][g]
-                um = sp["Umasks"][g] if sp.get("Umasks") else sp["Umask"]
-                out.append((U, ("dU", li, g), self.emask.get(id(U), um)))
-            if sp["bn"]:
-                for g in range(self.G):
-                    out.append((sp["bnm"][g].weight, ("dgamma", li, g), None))
-                    out.append((sp["bnm"][g].bias, ("dbeta", li, g), None))
-            if sp.get("ln"):
-                out.append((sp["ln_gamma"], ("dgamma_ln", li, 0), None))
-                out.append((sp["ln_beta"], ("dbeta_ln", li, 0), None))
-        return out
-
-    def quant_of(self, p):
-        q = self.qw.get(id(p))
-        if q is None:
-            return None, 0
-        return q
-
-    def wq(self, li, kind, g):
-        """The weight a GEMM / the time loop multiplies with (fake-quantised when quantised)."""
-        p = self.layers[li][kind][g]
-        q = self.qw.get(id(p))
-        return q[0] if q is not None else p
-
-
-class StdRecNode(RecNode):
-    """A whole LSTM_cudnn / GRU_cudnn / RNN_cudnn architecture (torch.nn.LSTM / GRU / RNN) as one
-    graph node: per layer and direction a packed weight_ih (G*H, K), weight_hh (G*H, H) and the two
-    biases, the standard-cell time loops of pkc_rnn_std_fwd / _bwd, dropout between layers.
-    layer_specs() contract: dict(std, H, act, bidir, ndir, drop (of the layer's output; 0 on the
-    last), W / U / bih / bhh: one entry per direction (biases None without bias))."""
-    std = True
-
-    def __init__(self, arch, net, K):
-        self.arch, self.net, self.K = arch, net, K
-        self.name = arch
-        self.std_cell = net.std_cell
-        self.cell = None                 # none of the pkc_rnn_args cells
-        self.cid = {"lstm": L.STD_LSTM, "gru": L.STD_GRU, "rnn": L.STD_RNN}[net.std_cell]
-        self.G = net.STD_GATES
-        # gate-gradient slabs per row: the GRU keeps r * da_n (recurrent side) beside da_n
-        self.GD = 4 if net.std_cell == "gru" else self.G
-        self.cand = None
-        self.layers = net.layer_specs()
-        self.N = net.out_dim
-        self.src = None
-        self.consumers = []
-        self.loss_weight = 0.0
-        self.label_col = None
-        for sp in self.layers:
-            if sp["act"] not in ("tanh", "relu"):
-                raise NotImplementedError("%s: nonlinearity %s (tanh or relu)" % (arch, sp["act"]))
-            if not 0.0 <= sp["drop"] < 1.0:
-                raise ValueError("%s: dropout %s outside [0, 1)" % (arch, sp["drop"]))
-        self.ibits = 0
-        self.reads = 0
-        self.qw = {}
-        self.emask = {}
-
-    def params(self):
-        out = []
-        for li, sp in enumerate(self.layers):
-            for d in range(sp["ndir"]):
-                out.append((sp["W"][d], ("dW", li, d), None))
-                out.append((sp["U"][d], ("dU", li, d), None))
-                if sp["bih"][d] is not None:
-                    out.append((sp["bih"][d], ("dbih", li, d), None))
-                    out.append((sp["bhh"][d], ("dbhh", li, d), None))
-        return out
-
-
-def pattern_effective_masks(net, s):
-    """Pattern masks (neural_networks.py:263-272, 876-884; sparsity.py:1112-1146) of one
-    architecture: computed once, at the first layer call, from |W| of every pattern-masked weight —
-    layer 0's input weights already multiplied by their HCGS mask, every other weight raw — and
-    then multiplied into all of them once per layer call (L times per forward; {0,1} except on
-    tied tiles).  Masks already held in ``net.pattern_mask`` (carried between chunks by run_nn,
-    core.py:129-131, 304-306) are reused, as the reference does; new ones are stored there in the
-    reference's structure.  Each weight's pattern set is, in order: the one carried in
-    ``net.pattern``; the shared set (``pattern_kernels`` / ``pattern_from_file``); or a KMeans
-    search of that weight (update_patterns, neural_networks.py:339-348, 1162-1172), stored back
-    into ``net.pattern``.  Returns {id(param): HCGS x pattern^L effective mask}."""
-    if not getattr(net, "if_pattern", False):
-        return {}
-    dev = next(net.parameters()).device
-    entries = net.pattern_params()
-    nl = 1 + max(e[1] for e in entries)
-    store, pstore = net.pattern_mask, net.pattern
-    have = all(_pm_get(store, key) is not None for key, _, _, _ in entries)
-    shared = net.pattern_kernels
-    if shared is None and not have and not net.can_search_patterns():
-        raise NotImplementedError("%s: pattern masks need a pattern set" % net.arch_name)
-    out = {}
-    for key, li, p, hmask in entries:
-        rows, cols = p.shape
-        if have:
-            pm = _pm_get(store, key).to(dev, torch.float32).contiguous()
-        else:
-            pre = li == 0 and hmask is not None and _is_input_weight(key)
-            src = (p * hmask if pre else p).contiguous()
-            pk = _pm_get(pstore, _pattern_key(key))
-            if pk is not None:
-                t = pk.detach().cpu().numpy() if torch.is_tensor(pk) else np.asarray(pk)
-                pk = t.reshape(t.shape[0], t.shape[-2], t.shape[-1]).astype(np.float32)
-            elif shared is not None:
-                pk = shared
-            else:                               # update_patterns: one KMeans search per weight
-                pn, shape, nnz = net.pattern_search_args(li)
-                pk = kmeans_patterns(src, pn, shape, nnz, random_state=net.pattern_seed)
-            P, ph, pw = pk.shape
-            if rows % ph or cols % pw:
-                raise NotImplementedError("%s: %dx%d weight not tiled by %dx%d patterns"
-                                          % (net.arch_name, rows, cols, ph, pw))
-            pat = torch.from_numpy(np.ascontiguousarray(pk, dtype=np.float32)).to(dev)
-            pm = torch.empty_like(p)
-            call("pkc_pattern_mask", ptr(src), rows, cols, ptr(pat), P, ph, pw, ptr(pm), s)
-            _pm_set(store, key, pm)
-            if _pm_get(pstore, _pattern_key(key)) is None:
-                _pm_set(pstore, _pattern_key(key), pat.view(P, 1, ph, pw))
-        e = pm.pow(nl) if nl > 1 else pm.clone()
-        out[id(p)] = e * hmask if hmask is not None else e
-    return out
-
-
-def _pattern_key(key):
-    """net.pattern key of a net.pattern_mask key: (None, i) for an MLP layer, ('pattern_wfx', i)
-    for ('pattern_mask_wfx', i) of an LSTM (neural_networks.py:1162-1172)."""
-    name, i = key
-    return (None if name is None else name.replace("pattern_mask_", "pattern_"), i)
-
-
-def _is_input_weight(key):
-    name, _ = key
-    return name is None or name.startswith("pattern_mask_w")
-
-
-def _pm_get(store, key):
-    name, i = key
-    lst = store if name is None else store.get(name, [])
-    return lst[i] if i < len(lst) else None
-
-
-def _pm_set(store, key, v):
-    name, i = key
-    lst = store if name is None else store.setdefault(name, [])
-    while len(lst) <= i:
-        lst.append(None)
-    lst[i] = v
+    def on_half(self):
+        """The operation on its bf16 operand copies (PKC_PREC_BF16IN)."""
+        return Op(self.label, self.flops, *self.half)
 
 
 class Engine:
@@ -782,6 +290,10 @@ class Engine:
         self.rnn_drop_in = rnn_drop_in or {}
         # the step form is fixed when the engine is built (module switches read once, here)
         self.rnn_bf16_sparse = RNN_BF16_SPARSE
+        # set later, on some paths only: weighted RegTerms, bf16-only dz / output addresses, updates
+        # waiting for the next forward (OPT_FWD), tests' record of dL/dy slabs, the bound chunk
+        self.reg_terms, self.scratch_dz, self.dead_out = [], None, None
+        self.fwd_opt = self.rec_dy_trace = self._chunk_key = None
         self._build_graph()
         self._alloc()
         self._build_masks()
@@ -824,72 +336,49 @@ class Engine:
                 K = produced[b].N
             else:
                 raise ValueError("input %s of %s is neither a feature nor a produced output" % (b, a))
+            # input LayerNorm / BatchNorm (a recurrent arch's over the T*B rows,
+            # neural_networks.py:1511-1516 ...)
+            for i, spec in enumerate(net.input_norm_specs() if hasattr(net, "input_norm_specs")
+                                     else []):
+                src = self._chain(NormLayer(a, i, spec, K), src)
             if getattr(net, "seq_model", False):
                 # (src may be a feed-forward node over the T*B rows, e.g. the MLP_layers_first ->
                 # liGRU of TIMIT_mfcc_fbank_fmllr_liGRU_best.cfg: its gradient is the recurrent
                 # layer 0's dX slabs, handed over in _rec_bwd)
-                # input LayerNorm / BatchNorm over the T*B rows (neural_networks.py:1511-1516 ...)
-                for i, spec in enumerate(net.input_norm_specs() if hasattr(net, "input_norm_specs")
-                                         else []):
-                    nl = NormLayer(a, i, spec, K)
-                    nl.src = src
-                    if src[0] == "node":
-                        src[1].consumers.append(nl)
-                    self.nodes.append(nl)
-                    src = ("node", nl)
                 node = (StdRecNode if hasattr(net, "std_cell") else RecNode)(a, net, K)
                 node.src = src
                 if src[0] == "node":
-                    if getattr(src[1], "rec_consumer", None) is not None:
+                    if src[1].rec_consumer is not None:
                         raise NotImplementedError("%s: read by two recurrent archs" % src[1].name)
                     src[1].rec_consumer = node      # its gradient: the rec layer-0 dX slabs
                 self.nodes.append(node)
                 produced[out] = node
                 continue
-            prev = src
-            for i, spec in enumerate(net.input_norm_specs() if hasattr(net, "input_norm_specs")
-                                     else []):
-                nl = NormLayer(a, i, spec, K)
-                nl.src = prev
-                if prev[0] == "node":
-                    prev[1].consumers.append(nl)
-                self.nodes.append(nl)
-                prev = ("node", nl)
             if hasattr(net, "conv_specs"):       # CNN: one node per Conv1d + max-pool layer
                 if self.sync_bn is not None and any(sp["bn"] for sp in net.conv_specs()):
                     raise NotImplementedError("sync_bn: %s has a BatchNorm'd convolution layer "
                                               "(per-rank statistics)" % a)
                 for i, spec in enumerate(net.conv_specs()):
-                    cn = ConvNode(a, i, spec, K)
-                    cn.src = prev
-                    if prev[0] == "node":
-                        prev[1].consumers.append(cn)
-                    self.nodes.append(cn)
-                    prev = ("node", cn)
-                    K = cn.N
-                produced[out] = prev[1]
+                    src = self._chain(ConvNode(a, i, spec, K), src)
+                    K = src[1].N
+                produced[out] = src[1]
                 continue
             for i, spec in enumerate(net.layer_specs()):
-                lay = Layer(a, i, spec, K)
-                lay.src = prev
-                if prev[0] == "node":
-                    prev[1].consumers.append(lay)
-                self.nodes.append(lay)
-                prev = ("node", lay)
-                K = lay.N
-                if lay.head and i != len(net.dnn_lay) - 1:
+                src = self._chain(Layer(a, i, spec, K), src)
+                K = src[1].N
+                if src[1].head and i != len(net.dnn_lay) - 1:
                     raise NotImplementedError("softmax only as the last layer of an MLP")
-            produced[out] = prev[1]
+            produced[out] = src[1]
         scal, self.err_layer, mse_terms = {}, None, []
         for out, op, a, b in self.lines:
             if op in TENSOR_OPS and (out in produced or out in self.fea_cols):
                 continue                        # a tensor operation: a node or a column range
-            if op in ("cost_nll", "cost_err") and getattr(produced.get(a), "combine", False):
+            if op in ("cost_nll", "cost_err") and produced.get(a, Node).combine:
                 raise NotImplementedError("%s on the combine output %s (%s) is not on the pkc path"
                                           % (op, a, produced[a].name))
-            if op == "mse" and any(getattr(produced.get(t), "combine", False) for t in (a, b)):
+            if op == "mse" and any(produced.get(t, Node).combine for t in (a, b)):
                 raise NotImplementedError("mse on the combine output %s is not on the pkc path"
-                                          % (a if getattr(produced.get(a), "combine", False) else b))
+                                          % (a if produced.get(a, Node).combine else b))
             if op == "cost_nll":
                 lay = produced[a]
                 if not lay.head:
@@ -994,12 +483,11 @@ class Engine:
             else:
                 raise NotImplementedError("[model] operation %s is not on the pkc path" % op)
         for n in self.nodes:
-            if getattr(n, "rec_consumer", None) is not None and n.consumers:
+            if n.rec_consumer is not None and n.consumers:
                 # its gradient would be the recurrent dX slabs AND the other consumers' slabs (an
                 # mse term on it is fine: that writes one more slab beside the recurrent ones)
                 raise NotImplementedError("%s: read by a recurrent arch and by other archs" % n.name)
-            if getattr(n, "combine", False) and n.heads_in and (
-                    n.consumers or getattr(n, "rec_consumer", None) is not None):
+            if n.combine and n.heads_in and (n.consumers or n.rec_consumer is not None):
                 # (the posterior ensemble: an avg of two heads named in forward_out, no gradient)
                 raise NotImplementedError("%s: a combine of LogSoftmax heads that has a consumer "
                                           "is not on the pkc path" % n.name)
@@ -1027,6 +515,14 @@ class Engine:
                 lay.label_col = -1
         self.layers = [n for n in self.nodes if not n.rec]     # dense layers (compat)
         self._build_quant()
+
+    def _chain(self, node, src):
+        """Append `node` to the graph behind `src`; returns it as the next source."""
+        node.src = src
+        if src[0] == "node":
+            src[1].consumers.append(node)
+        self.nodes.append(node)
+        return ("node", node)
 
     def _combine_line(self, out, op, a, b, produced):
         """One [model] tensor-operation line into a CombineNode (or nothing: a concatenate that
@@ -1077,7 +573,7 @@ class Engine:
         that tensor uses the final version (autograd saved the same tensor object)."""
         self.qsrc = {}
         for n in self.nodes:
-            if getattr(n, "combine", False):
+            if n.combine:
                 continue
             key = ("fea", n.src[1], n.src[2]) if n.src[0] == "fea" else id(n.src[1])
             ent = self.qsrc.setdefault(key, dict(bits=0, Q=0, src=n.src))
@@ -1097,7 +593,7 @@ class Engine:
                 raise NotImplementedError("%s: %s output quantised in place by a consumer" %
                                           (P.name, P.act))
         for n in self.nodes:
-            if not getattr(n, "combine", False):
+            if not n.combine:
                 continue
             # the combine would have to read the version current when its line runs, and its
             # backward the version autograd saved: not modelled, so refused
@@ -1122,10 +618,10 @@ class Engine:
             if n.rec:
                 self._alloc_rec(n)
                 continue
-            if getattr(n, "conv", False):
+            if n.conv:
                 self._alloc_conv(n)
                 continue
-            if getattr(n, "combine", False):
+            if n.combine:
                 n.out = _f32(M * n.N, dev)
                 continue
             N, K = n.N, n.K
@@ -1167,7 +663,7 @@ class Engine:
             ent["work"] = _f32(256, dev)
         for n in self.nodes:
             # (a recurrent consumer's layer-0 dX buffer holds the mse slabs otherwise, _alloc_rec)
-            cap = 0 if getattr(n, "rec_consumer", None) is not None else len(n.mse_grad)
+            cap = 0 if n.rec_consumer is not None else len(n.mse_grad)
             for c in n.consumers:
                 # an input norm (no matmul) writes its input gradient into one slab
                 c.sxcap = 1 if c.W is None else (self.cap or _splits(
@@ -1176,7 +672,7 @@ class Engine:
             n.gslab = _f32(cap * M * n.N, dev) if cap else None
         self.needs_grad = {}
         for n in reversed(self.nodes):
-            rc = getattr(n, "rec_consumer", None)
+            rc = n.rec_consumer
             self.needs_grad[n] = self.external or (n.head and n.loss_weight != 0.0) or any(
                 self.needs_grad[c] for c in n.consumers) or (
                     rc is not None and self.needs_grad[rc]) or bool(n.mse_grad)
@@ -1266,9 +762,6 @@ class Engine:
         self.h16 = (bool(want) and self.prec == L.PREC_BF16 and not self.seq and not self.prune_list
                     and not any(ent["Q"] for ent in self.qsrc.values()))
         self.x_h = None
-        for n in self.nodes:
-            n.W_h = n.out_h = n.dz_h = None
-            n.f32_dead = n.dz_scratch = False
         self.scratch_dz = set()
         self.dead_out = set()
         if not self.h16:
@@ -1279,8 +772,7 @@ class Engine:
             self.x_h = torch.zeros(M * self.F, dtype=bf, device=dev)
         keep_f32 = os.environ.get("PKC_F32_OUT", "0") != "0"
         for n in self.nodes:                # a conv / combine node's output for its bf16 consumer matmuls
-            if (getattr(n, "conv", False) or getattr(n, "combine", False)) and any(
-                    c in mm for c in n.consumers):
+            if (n.conv or n.combine) and any(c in mm for c in n.consumers):
                 n.out_h = torch.zeros(M * n.N, dtype=bf, device=dev)
         for n in mm:
             n.W_h = torch.zeros(n.W.numel(), dtype=bf, device=dev)
@@ -1295,8 +787,7 @@ class Engine:
                               and not any(t.node is n for t in self.mse_terms)
                               and all(c in mm and not c.ln and self.needs_grad[c]
                                       for c in n.consumers)
-                              and not any(getattr(c, "qv0", 0) or getattr(c, "reads", 0)
-                                          for c in n.consumers))
+                              and not any(c.qv0 or c.reads for c in n.consumers))
             if self.needs_grad[n] and not n.ln:
                 n.dz_h = torch.zeros(M * n.N, dtype=bf, device=dev)
         # every matmul of the step has bf16 operand copies (so every launch runs PKC_PREC_BF16IN):
@@ -1312,7 +803,7 @@ class Engine:
                 self.dead_out.add(n.out.data_ptr())
         for e in self.opt_entries:
             nd = e["node"]
-            if nd is not None and getattr(nd, "W_h", None) is not None and e["p"] is nd.W:
+            if nd is not None and nd.W_h is not None and e["p"] is nd.W:
                 e["bout"] = nd.W_h
         if self.opt_entries:
             self._upload_opt_desc(step_inc=1)
@@ -1323,7 +814,7 @@ class Engine:
         the optimizer, which keeps them current itself)."""
         s = self._stream()
         for n in self.nodes:
-            if getattr(n, "W_h", None) is not None:
+            if n.W_h is not None:
                 call("pkc_cast_bf16", ptr(n.W), ptr(n.W_h), n.W.numel(), s)
 
     def _alloc_std(self, n):
@@ -1358,7 +849,7 @@ class Engine:
         n.out = n.lbuf[-1]["y"]
 
     def _alloc_rec(self, n):
-        if getattr(n, "std", False):
+        if n.std:
             return self._alloc_std(n)
         M, dev, B, T = self.Mmax, self.dev, self.B, self.max_len
         G = n.G
@@ -1542,7 +1033,7 @@ class Engine:
         self.opt_entries = []
         self._host_maps, self._seg_keep = {}, {}
         for n in self.nodes:
-            if not self.needs_grad[n] or self.external or getattr(n, "combine", False):
+            if not self.needs_grad[n] or self.external or n.combine:
                 continue
             o = self.arch_opts[n.arch]
             if _b(o.get("arch_freeze", "False")):
@@ -1558,7 +1049,7 @@ class Engine:
                                              node=n))
         # mask Parameters trained by a regulariser term only (their gradient is the term's)
         seen = {id(e["p"]) for e in self.opt_entries}
-        for t in getattr(self, "reg_terms", []):
+        for t in self.reg_terms:
             for p, arch in t.masks:
                 o = self.arch_opts[arch]
                 if id(p) in seen or _b(o.get("arch_freeze", "False")) or not self.train:
@@ -1742,7 +1233,7 @@ class Engine:
         assert feats.dtype == torch.float32 and labels.dtype == torch.int32
         assert feats.shape[1] >= self.F and labels.shape[1] == self.nlab
         key = (feats.data_ptr(), feats.stride(0), labels.data_ptr())
-        if self.seq_graphs is not None and key != getattr(self, "_chunk_key", None):
+        if self.seq_graphs is not None and key != self._chunk_key:
             self.seq_graphs.clear()            # the captured gathers read the old chunk
             self.seq_seen = {}
         self._chunk_key = key
@@ -1808,7 +1299,7 @@ class Engine:
         if n.src[0] == "fea":
             return None if self.x_h is None else self.x_h.data_ptr() + 2 * n.src[1]
         P = n.src[1]
-        return None if getattr(P, "out_h", None) is None else P.out_h.data_ptr()
+        return None if P.out_h is None else P.out_h.data_ptr()
 
     @staticmethod
     def _h_variant(pr, A, B):
@@ -1888,7 +1379,7 @@ class Engine:
             last = pos[first[n]] - 1 if first.get(n) is not None else 0
             cands = [k for k in order[:max(1, last + 1)] if load[k][1] < 8]
             k = min(cands, key=lambda c: load[c][0]) if cands else None
-            load[k][0] += op[2]
+            load[k][0] += op.nbytes
             load[k][1] += 1
             slots.setdefault(k, []).append(op)
         return slots
@@ -1920,10 +1411,10 @@ class Engine:
                           ldb=self.nlab, C=self.x.data_ptr(), slab_stride=self.n_batches,
                           X1=self.ctr.data_ptr(), X2=self.labs.data_ptr(),
                           X3=self.x_h.data_ptr() if self.x_h is not None else None)
-        return ("gather", 0.0, 8.0 * M * self.F, p)
+        return Op("gather", 0.0, 8.0 * M * self.F, p)
 
     def _fwd_problem(self, n):
-        """(label, flops, bytes, GemmProblem) of a dense layer's forward matmul Z = X W^T."""
+        """The Op of a dense layer's forward matmul Z = X W^T."""
         M = self.M
         a_ptr, lda = self._version(n, n.qv0 + n.reads)
         kt = self._wt(n.W, False)
@@ -1938,57 +1429,45 @@ class Engine:
             pr.ktiles, pr.kmax, d = kt[0].data_ptr(), kt[1], kt[2]
         prh = self._h_variant(pr, self._src_h(n) if not (n.qv0 + n.reads) else None,
                               n.W_h.data_ptr() if n.W_h is not None else None)
-        return ("fwd %dx%dx%d%s" % (M, n.N, n.K, " sparse %.2f" % d if kt is not None else ""),
-                2.0 * M * n.N * n.K * d, 4.0 * (M * n.K + n.N * n.K * d + sf * M * n.N), pr,
-                None if prh is None else (2.0 * (M * n.K + n.N * n.K * d) + 4.0 * sf * M * n.N, prh))
+        return Op("fwd %dx%dx%d%s" % (M, n.N, n.K, " sparse %.2f" % d if kt is not None else ""),
+                  2.0 * M * n.N * n.K * d, 4.0 * (M * n.K + n.N * n.K * d + sf * M * n.N), pr,
+                  None if prh is None else (2.0 * (M * n.K + n.N * n.K * d) + 4.0 * sf * M * n.N, prh))
 
     def _gemms(self, probs, s):
-        """Launch matmul problems: one pkc_gemm, or pkc_gemm_grouped for several (<= 8 each).
-        A launch whose matmuls all have bf16 operand copies (a 5th tuple item: (bytes, problem))
-        runs on them (PKC_PREC_BF16IN); its other operations are precision-neutral."""
+        """Launch operations (Op): one pkc_gemm, or pkc_gemm_grouped for several (<= 8 each).
+        A launch whose matmuls all have bf16 operand copies (Op.half) runs on them
+        (PKC_PREC_BF16IN); its other operations are precision-neutral."""
         for i in range(0, len(probs), 8):
             # dX problems lead the launch: at a workgroup offset that is a multiple of 8 (the
             # preceding dX grids have 16k-wide tile rows), tile j of a 1024-column dX runs on XCD
             # j % 8 — the XCD whose BatchNorm-backward workgroups read that tile's slabs
             # (pkc_dense.hip col_group<2>)
-            part = sorted(probs[i:i + 8], key=lambda q: 0 if q[0].startswith("dX") else 1)
-            gem = [q for q in part if q[3].kind == L.OP_GEMM]
+            part = sorted(probs[i:i + 8], key=lambda q: 0 if q.label.startswith("dX") else 1)
+            gem = [q for q in part if q.prob.kind == L.OP_GEMM]
             prec = self.prec
-            if gem and all(len(q) > 4 and q[4] is not None for q in gem):
+            if gem and all(q.half is not None for q in gem):
                 prec = L.PREC_BF16IN
-                part = [(q[0], q[1]) + tuple(q[4]) if len(q) > 4 and q[4] is not None else q[:4]
-                        for q in part]
+                part = [q.on_half() if q.half is not None else q for q in part]
             else:
-                part = [q[:4] for q in part]
-                sd = getattr(self, "scratch_dz", None)
-                if sd and any(q[3].A in sd or q[3].B in sd for q in part):
+                sd = self.scratch_dz
+                if sd and any(q.prob.A in sd or q.prob.B in sd for q in part):
                     raise RuntimeError("fp32 matmul on a bf16-only gradient: %s"
-                                       % [q[0] for q in part])
-                do = getattr(self, "dead_out", None)
-                if do and any(q[3].kind == L.OP_GEMM and (q[3].A in do or q[3].B in do)
+                                       % [q.label for q in part])
+                do = self.dead_out
+                if do and any(q.prob.kind == L.OP_GEMM and (q.prob.A in do or q.prob.B in do)
                               for q in part):
                     raise RuntimeError("fp32 matmul on a layer output stored as bf16 only: %s"
-                                       % [q[0] for q in part])
-            if len(part) == 1 and part[0][3].kind == L.OP_GEMM and not part[0][3].ktiles:
-                lab, fl, nb, p = part[0]
-                self._k("gemm_" + lab, fl, nb, "pkc_gemm", prec, p.a_kcontig, p.b_kcontig,
-                        p.M, p.N, p.K, C.c_void_p(p.A), p.lda, C.c_void_p(p.B), p.ldb,
+                                       % [q.label for q in part])
+            if len(part) == 1 and part[0].prob.kind == L.OP_GEMM and not part[0].prob.ktiles:
+                q, p = part[0], part[0].prob
+                self._k("gemm_" + q.label, q.flops, q.nbytes, "pkc_gemm", prec, p.a_kcontig,
+                        p.b_kcontig, p.M, p.N, p.K, C.c_void_p(p.A), p.lda, C.c_void_p(p.B), p.ldb,
                         C.c_void_p(p.C), p.ldc, p.splits, p.slab_stride, s)
             else:
-                arr = (L.GemmProblem * len(part))(*[q[3] for q in part])
-                self._k("gemm_group[" + ", ".join(q[0] for q in part) + "]",
-                        sum(q[1] for q in part), sum(q[2] for q in part), "pkc_gemm_grouped",
+                arr = (L.GemmProblem * len(part))(*[q.prob for q in part])
+                self._k("gemm_group[" + ", ".join(q.label for q in part) + "]",
+                        sum(q.flops for q in part), sum(q.nbytes for q in part), "pkc_gemm_grouped",
                         prec, arr, len(part), s)
-
-    def _dense_fwd(self, n, s, train):
-        self._quant_chain(n, s)
-        prob = self._fwd_problem(n)
-        if self._fused_fwd(n, prob, s, train):
-            return
-        if train and self._colstats_fwd(n, prob, s):
-            return
-        self._gemms([prob], s)
-        self._fwd_epilogue(n, s, train)
 
     def _colstats_fwd(self, n, prob, s):
         """Large-batch BatchNorm'd MLP layer in training: the forward matmul writes the BatchNorm
@@ -1997,21 +1476,19 @@ class Engine:
         only; sequence models keep the stats-pass blocking their recurrent lifecycle tests are
         pinned to.  Returns False when not taken."""
         if not (COLSTATS and n.bn and not n.ln and not n.head and n.W is not None and not self.seq
-                and self.M > 128 and getattr(n, "bn_states", None) is None):
+                and self.M > 128 and n.bn_states is None):
             return False
-        lab, fl, nb, p = prob[:4]
-        if p.splits != 1 or p.ktiles:
+        if prob.prob.splits != 1 or prob.prob.ktiles:
             return False
-        prec = self.prec
-        if len(prob) > 4 and prob[4] is not None:
-            prec, (nb, p) = L.PREC_BF16IN, prob[4]
+        prec, q = (L.PREC_BF16IN, prob.on_half()) if prob.half is not None else (self.prec, prob)
+        p = q.prob
         rows = L.lib().pkc_gemm_colstats_ok(prec, p.a_kcontig, p.b_kcontig, p.M, p.N, p.K,
                                             C.c_void_p(p.A), p.lda, C.c_void_p(p.B), p.ldb)
         if rows <= 0:
             return False
-        self._k("gemm_colstats " + lab, fl, nb + 8.0 * p.N * -(-p.M // rows), "pkc_gemm_colstats",
-                prec, p.a_kcontig, p.b_kcontig, p.M, p.N, p.K, C.c_void_p(p.A), p.lda,
-                C.c_void_p(p.B), p.ldb, C.c_void_p(p.C), p.ldc, ptr(n.b), ptr(n.work), s)
+        self._k("gemm_colstats " + q.label, q.flops, q.nbytes + 8.0 * p.N * -(-p.M // rows),
+                "pkc_gemm_colstats", prec, p.a_kcontig, p.b_kcontig, p.M, p.N, p.K, C.c_void_p(p.A),
+                p.lda, C.c_void_p(p.B), p.ldb, C.c_void_p(p.C), p.ldc, ptr(n.b), ptr(n.work), s)
         self._fwd_epilogue(n, s, True, pre_rows=rows)
         return True
 
@@ -2054,7 +1531,7 @@ class Engine:
                     C.byref(a), s)
             return
         a = self._dense_fwd_args(n, train, zp, sf, zs, bias)
-        if train and n.bn and getattr(n, "bn_states", None) is not None:
+        if train and n.bn and n.bn_states is not None:
             # SyncBN: this rank's column state into its row of bn_states, all-reduce (gather),
             # merge + apply
             R, r = self.sync_bn.world, self.sync_bn.rank
@@ -2088,8 +1565,7 @@ class Engine:
             keep_in=keep_in.data_ptr() if keep_in is not None else None,
             keep_out=n.keep.data_ptr() if (n.keep is not None and train) else None,
             xhat=n.xhat.data_ptr(), count_n=0,
-            out=None if (train and getattr(n, "f32_dead", False)
-                         and getattr(n, "bn_states", None) is None) else n.out.data_ptr(),
+            out=None if (train and n.f32_dead and n.bn_states is None) else n.out.data_ptr(),
             out_bf16=n.out_h.data_ptr() if n.out_h is not None else None)
 
     def _fused_fwd(self, n, prob, s, train, riding=()):
@@ -2100,22 +1576,20 @@ class Engine:
         precisions, block-sparse W, LayerNorm, SyncBN, operations riding in the forward launch)."""
         if not (FUSED_FWD and self.prec == L.PREC_BF16 and self.M <= 128 and not n.head
                 and n.W is not None and not n.ln and not riding
-                and getattr(n, "bn_states", None) is None):
+                and n.bn_states is None):
             return False
-        lab, fl, nb, p = prob[:4]
-        if p.ktiles:
+        if prob.prob.ktiles:
             return False
-        prec = L.PREC_BF16
-        if len(prob) > 4 and prob[4] is not None:
-            prec, (nb, p) = L.PREC_BF16IN, prob[4]
+        prec, q = (L.PREC_BF16IN, prob.on_half()) if prob.half is not None else (self.prec, prob)
+        p = q.prob
         if not L.lib().pkc_dense_gemm_fwd_ok(prec, p.M, p.N, p.K, C.c_void_p(p.A), p.lda,
                                              C.c_void_p(p.B), p.ldb):
             return False
         n.sf = 1
         a = self._dense_fwd_args(n, train, None, 1, 0, n.b.data_ptr())
-        self._k("fused_fwd %dx%dx%d" % (p.M, p.N, p.K), fl, nb - 4.0 * p.splits * p.M * p.N +
-                4.0 * p.M * p.N * 2, "pkc_dense_gemm_fwd", prec, C.c_void_p(p.A), p.lda,
-                C.c_void_p(p.B), p.ldb, p.K, C.byref(a), s)
+        self._k("fused_fwd %dx%dx%d" % (p.M, p.N, p.K), q.flops,
+                q.nbytes - 4.0 * p.splits * p.M * p.N + 4.0 * p.M * p.N * 2, "pkc_dense_gemm_fwd",
+                prec, C.c_void_p(p.A), p.lda, C.c_void_p(p.B), p.ldb, p.K, C.byref(a), s)
         return True
 
     def _rnn_args(self, n, li, train, T):
@@ -2190,7 +1664,7 @@ class Engine:
         for n in self.nodes:
             if not n.rec:
                 continue
-            if getattr(n, "std", False):      # standard cells: one exact-fp32 launch per step
+            if n.std:                         # standard cells: one exact-fp32 launch per step
                 for li in range(len(n.layers)):
                     out["%s.%d" % (n.arch, li)] = "fp32 steps"
                 continue
@@ -2288,12 +1762,7 @@ class Engine:
         d weight_hh = dR^T h_{t-1} and the bias column sums, then the dX = dA weight_ih slabs (the
         next layer's dL/dy; its dropout is applied where that layer's loop reads them)."""
         M, T, B = self.M, self.T, self.B
-        gs = getattr(n, "gsrc", None)
-        if gs is not None:
-            dy_t, dy_ns, dy_stride = gs[0], gs[1], gs[2]
-        else:
-            dy_t, dy_ns = n.gslab, n.sb
-            dy_stride = M * n.N
+        dy_t, dy_ns, dy_stride = self._out_grad(n)
         dy_ptr = dy_t.data_ptr()
         G, GD, gru = n.G, n.GD, n.std_cell == "gru"
         for li in reversed(range(len(n.layers))):
@@ -2319,37 +1788,37 @@ class Engine:
                 # (GRU rows [r, z, n_rec, n_in]: r, z and n_in; else all G gates)
                 cols = [(0, 2 * H, 0), (3 * H, H, 2 * H)] if gru else [(0, GH, 0)]
                 for c0, w, r0 in cols:
-                    wg.append(("dWih%d %dx%dx%d" % (d, w, K, M), 2.0 * w * K * M,
-                               4.0 * (M * w + M * K + w * K),
-                               L.GemmProblem(a_kcontig=0, b_kcontig=0, M=w, N=K, K=M, splits=1,
-                                             A=dg + 4 * c0, lda=GDH, B=x_ptr, ldb=ldx,
-                                             C=dW + 4 * r0 * K, ldc=K, slab_stride=0)))
+                    wg.append(Op("dWih%d %dx%dx%d" % (d, w, K, M), 2.0 * w * K * M,
+                                 4.0 * (M * w + M * K + w * K),
+                                 L.GemmProblem(a_kcontig=0, b_kcontig=0, M=w, N=K, K=M, splits=1,
+                                               A=dg + 4 * c0, lda=GDH, B=x_ptr, ldb=ldx,
+                                               C=dW + 4 * r0 * K, ldc=K, slab_stride=0)))
                     if want_dx:
                         sx = _splits(M, K, w, MAX_SPLITS)
-                        dxp.append(("dX%d %dx%dx%d" % (d, M, K, w), 2.0 * M * K * w,
-                                    4.0 * (M * w + w * K + sx * M * K),
-                                    L.GemmProblem(a_kcontig=1, b_kcontig=0, M=M, N=K, K=w, splits=sx,
-                                                  A=dg + 4 * c0, lda=GDH,
-                                                  B=sp["W"][d].data_ptr() + 4 * r0 * K, ldb=K,
-                                                  C=lb["dx"].data_ptr() + 4 * nx * M * K, ldc=K,
-                                                  slab_stride=M * K)))
+                        dxp.append(Op("dX%d %dx%dx%d" % (d, M, K, w), 2.0 * M * K * w,
+                                      4.0 * (M * w + w * K + sx * M * K),
+                                      L.GemmProblem(a_kcontig=1, b_kcontig=0, M=M, N=K, K=w, splits=sx,
+                                                    A=dg + 4 * c0, lda=GDH,
+                                                    B=sp["W"][d].data_ptr() + 4 * r0 * K, ldb=K,
+                                                    C=lb["dx"].data_ptr() + 4 * nx * M * K, ldc=K,
+                                                    slab_stride=M * K)))
                         nx += sx
-                wg.append(("dWhh%d %dx%dx%d" % (d, GH, H, M), 2.0 * GH * H * M,
-                           4.0 * (M * GH + M * H + GH * H),
-                           L.GemmProblem(a_kcontig=0, b_kcontig=0, M=GH, N=H, K=M, splits=1, A=dg,
-                                         lda=GDH, B=hp, ldb=H, C=dU, ldc=H, slab_stride=0)))
+                wg.append(Op("dWhh%d %dx%dx%d" % (d, GH, H, M), 2.0 * GH * H * M,
+                             4.0 * (M * GH + M * H + GH * H),
+                             L.GemmProblem(a_kcontig=0, b_kcontig=0, M=GH, N=H, K=M, splits=1, A=dg,
+                                           lda=GDH, B=hp, ldb=H, C=dU, ldc=H, slab_stride=0)))
                 if lb["dbih"][d] is not None:
                     # column sums of the whole gate-gradient rows, then the two biases' ranges
                     # (bias_hh: the recurrent side — for the GRU's b_hn, sum r da_n)
                     bt = lb["dbt"].data_ptr() + 4 * d * GDH
                     bi, bh = lb["dbih"][d].data_ptr(), lb["dbhh"][d].data_ptr()
-                    wg.append(("db%d colsum %dx%d" % (d, M, GDH), 0.0, 4.0 * M * GDH,
-                               L.GemmProblem(kind=L.OP_COLSUM, M=M, N=GDH, A=dg, C=bt)))
+                    wg.append(Op("db%d colsum %dx%d" % (d, M, GDH), 0.0, 4.0 * M * GDH,
+                                 L.GemmProblem(kind=L.OP_COLSUM, M=M, N=GDH, A=dg, C=bt)))
 
                     def cp(src, dst, cnt, lab):
-                        return ("db%d copy %s" % (d, lab), 0.0, 8.0 * cnt,
-                                L.GemmProblem(kind=L.OP_SLABSUM, M=1, N=cnt, A=src, C=dst,
-                                              slab_stride=cnt))
+                        return Op("db%d copy %s" % (d, lab), 0.0, 8.0 * cnt,
+                                  L.GemmProblem(kind=L.OP_SLABSUM, M=1, N=cnt, A=src, C=dst,
+                                                slab_stride=cnt))
                     tail.append(cp(bt, bh, GH, "hh"))
                     if gru:
                         tail += [cp(bt, bi, 2 * H, "ih rz"), cp(bt + 12 * H, bi + 8 * H, H, "ih n")]
@@ -2368,7 +1837,7 @@ class Engine:
                 self._rec_slab_sum_ptr(lb["dx"].data_ptr(), nx, M * K, M * K, self.ext_dx, s)
 
     def _rec_fwd(self, n, s, train):
-        if getattr(n, "std", False):
+        if n.std:
             return self._std_fwd(n, s, train)
         M, T = self.M, self.T
         self._quant_chain(n, s)
@@ -2438,20 +1907,15 @@ class Engine:
         nodes, i = self.nodes, 0
         while i < len(nodes):
             n = nodes[i]
-            if n.rec:
-                self._rec_fwd(n, s, train)
-                i += 1
-                continue
-            if getattr(n, "conv", False):
-                self._conv_fwd(n, s, train)
-                i += 1
-                continue
-            if getattr(n, "combine", False):
-                self._combine_fwd(n, s)
-                i += 1
-                continue
-            if n.W is None:
-                self._fwd_epilogue(n, s, train)
+            if n.W is None:                  # no matmul of the engine's own in front
+                if n.rec:
+                    self._rec_fwd(n, s, train)
+                elif n.conv:
+                    self._conv_fwd(n, s, train)
+                elif n.combine:
+                    self._combine_fwd(n, s)
+                else:                        # an input normalisation
+                    self._fwd_epilogue(n, s, train)
                 i += 1
                 continue
             # output heads reading the same tensor (cd + mono senones) share one matmul launch
@@ -2484,7 +1948,7 @@ class Engine:
     def _mse_slabs(self, n):
         """(buffer, slab stride) holding node n's mse gradient slabs, in front of its other
         gradient slabs: a recurrent consumer's layer-0 dX buffer, or n's own gslab."""
-        rc = getattr(n, "rec_consumer", None)
+        rc = n.rec_consumer
         return (rc.lbuf[0]["dx"] if rc is not None else n.gslab), self.M * n.N
 
     def _mse_kernels(self, s, train):
@@ -2499,7 +1963,7 @@ class Engine:
             if train and t in n.mse_grad:
                 buf, st = self._mse_slabs(n)
                 dy = C.c_void_p(buf.data_ptr() + 4 * n.mse_grad.index(t) * st)
-                if getattr(n, "rec_consumer", None) is not None:
+                if n.rec_consumer is not None:
                     # (a recurrent consumer that takes no gradient never rewrites this)
                     n.gsrc = (buf, len(n.mse_grad), st)
             self._k("mse_fused %s N=%d" % (t.name, n.N), 3.0 * M * n.N,
@@ -2521,7 +1985,7 @@ class Engine:
         consumer matmul reads bf16)."""
         M = self.M
         a = self._combine_args(n)
-        out_h = getattr(n, "out_h", None)
+        out_h = n.out_h
         a.out, a.out_bf16 = n.out.data_ptr(), ptr(out_h)
         self._k("combine_fwd %s %dx%d" % (n.name, M, n.N), float(M * n.N),
                 4.0 * M * n.N * (2 if len(n.srcs) == 1 or n.op == "concatenate" else 3)
@@ -2532,11 +1996,8 @@ class Engine:
         a recurrent consumer's layer-0 dX slabs) into one slab of each producer that takes a
         gradient; no launch when neither operand does (feature streams)."""
         M = self.M
-        gs = getattr(n, "gsrc", None)
-        if gs is not None:
-            g_ptr, g_ns, g_st = gs[0].data_ptr(), gs[1], gs[2]
-        else:
-            g_ptr, g_ns, g_st = n.gslab.data_ptr(), n.sb, M * n.N
+        g_t, g_ns, g_st = self._out_grad(n)
+        g_ptr = g_t.data_ptr()
         dst = []
         for src, ci in zip(n.srcs, n.cons_idx):
             if src[0] == "node" and self.needs_grad[src[1]]:
@@ -2571,7 +2032,7 @@ class Engine:
         self._k("conv1d_fwd %s" % n.name, 2.0 * M * n.C_out * Lc * n.C_in * n.len,
                 4.0 * (M * n.K + n.cW.numel() + M * n.N) + M * n.N, "pkc_conv1d_fwd", C.byref(a), s)
         keep_in = self.drop_keep_in.get(n.name)
-        out_h = getattr(n, "out_h", None)
+        out_h = n.out_h
         pa = conv_post_args(
             sp, M, n.z, train, n.out, save_mean=n.save_mean.data_ptr(),
             save_invstd=n.save_invstd.data_ptr(), ln_stat=ptr(n.ln_stat),
@@ -2585,11 +2046,8 @@ class Engine:
         """A conv node's backward: dropout / activation / norm over its output gradient (the
         consumers' dX slabs, a recurrent consumer's, or the caller's), then dX / dW / dbias."""
         M, sp = self.M, n.spec
-        gs = getattr(n, "gsrc", None)
-        if gs is not None:
-            g_ptr, g_ns, g_st = gs[0].data_ptr(), gs[1], gs[2]
-        else:
-            g_ptr, g_ns, g_st = n.gslab.data_ptr(), n.sb, M * n.N
+        g_t, g_ns, g_st = self._out_grad(n)
+        g_ptr = g_t.data_ptr()
         dg, db = (n.dgamma_ln, n.dbeta_ln) if n.ln else (n.dgamma, n.dbeta) if n.bn else (None, None)
         pa = conv_post_args(
             sp, M, n.z, True, n.out, save_invstd=n.save_invstd.data_ptr(), ln_stat=ptr(n.ln_stat),
@@ -2624,7 +2082,7 @@ class Engine:
                           A=self.loss_ptrs.data_ptr(), B=self.loss_w.data_ptr(),
                           C=self.loss_out.data_ptr(), X1=self.err_layer.row_err.data_ptr(),
                           X2=self.loss_acc.data_ptr(), X3=None if self.seq else self.ctr.data_ptr())
-        return ("loss", 0.0, 4.0 * self.M * (self.n_loss_terms + 1), p)
+        return Op("loss", 0.0, 4.0 * self.M * (self.n_loss_terms + 1), p)
 
     def _nll_multi(self, heads, s, train):
         """LogSoftmax/NLL of several heads in one launch."""
@@ -2656,6 +2114,13 @@ class Engine:
             off += c.sx
         return off
 
+    def _out_grad(self, n):
+        """(buffer, slabs, slab stride) of dL/d(out of n): n.gsrc when set (a recurrent consumer's
+        layer-0 dX slabs, the caller's gradient in the external mode), else its consumers' dX slabs."""
+        if n.gsrc is not None:
+            return n.gsrc
+        return (n.gslab, n.sb, self.M * n.N) if n.gslab is not None else (None, 0, 0)
+
     def _dense_bwd_pre(self, n, s):
         """dL/dz of a dense layer: the fused dropout / activation / BatchNorm backward over the
         consumers' dX slabs (a head's dlogits came from the forward; its bias gradient is an
@@ -2663,12 +2128,8 @@ class Engine:
         M = self.M
         # gradient of n's output: its consumers' dX slabs (an input norm consumer writes one), or
         # a recurrent node's layer-0 dX slabs when n is that node's input norm
-        gs = getattr(n, "gsrc", None)
-        if gs is not None:
-            g_ptr, g_ns, g_st = gs[0].data_ptr(), gs[1], gs[2]
-        else:
-            g_ptr, g_ns, g_st = ((n.gslab.data_ptr(), n.sb, M * n.N) if n.gslab is not None
-                                 else (None, 0, 0))
+        g_t, g_ns, g_st = self._out_grad(n)
+        g_ptr = None if g_t is None else g_t.data_ptr()
         if n.W is None and n.ln:             # input LayerNorm: gamma / beta and input gradients
             self._ln_bwd(n, s, C.c_void_p(g_ptr), g_ns, g_st, self._norm_dx(n), None)
             return
@@ -2689,8 +2150,8 @@ class Engine:
                            dbeta=n.dbeta.data_ptr() if n.bn else None,
                            dbias=n.db.data_ptr() if (n.b is not None and not n.ln) else None,
                            dz_bf16=n.dz_h.data_ptr() if (n.W is not None and n.dz_h is not None)
-                           else None, dz_scratch=int(getattr(n, "dz_scratch", False)))
-        if n.bn and getattr(n, "bn_sums", None) is not None:
+                           else None, dz_scratch=int(n.dz_scratch))
+        if n.bn and n.bn_sums is not None:
             # SyncBN: local column sums (and local dgamma / dbeta), all-reduce, global apply
             self._k("dense_bwd_stats N=%d" % n.N, 0, 4.0 * M * n.N * (g_ns + 2), "pkc_dense_bwd_stats",
                     C.byref(a), ptr(n.work), ptr(n.bn_sums), s)
@@ -2698,7 +2159,7 @@ class Engine:
             self._k("dense_bwd_sync_apply N=%d" % n.N, 0, 4.0 * M * n.N * 3,
                     "pkc_dense_bwd_sync_apply", C.byref(a), ptr(n.work), ptr(n.bn_sums),
                     M * self.sync_bn.world, s)
-        elif getattr(n, "bnb_now", False):   # statistics came with the consumer's dX matmul
+        elif n.bnb_now:                      # statistics came with the consumer's dX matmul
             self._k("dense_bwd_pre N=%d" % n.N, 0, 4.0 * M * n.N * 3, "pkc_dense_bwd_pre",
                     C.byref(a), ptr(n.work), 128, s)
         else:
@@ -2733,19 +2194,19 @@ class Engine:
         a_ptr, lda = self._final_version(n) if self.qsrc[n.qkey]["Q"] else self._src(n)
         out = []
         if n.head and not n.ln:
-            out.append(("db %d" % n.N, 0.0, 4.0 * M * n.N,
-                        L.GemmProblem(kind=L.OP_COLSUM, M=M, N=n.N, A=n.dz.data_ptr(),
-                                      C=n.db.data_ptr())))
-        sdw = getattr(n, "sdw", 1)
-        dzh = n.dz_h.data_ptr() if getattr(n, "dz_h", None) is not None else None
+            out.append(Op("db %d" % n.N, 0.0, 4.0 * M * n.N,
+                          L.GemmProblem(kind=L.OP_COLSUM, M=M, N=n.N, A=n.dz.data_ptr(),
+                                        C=n.db.data_ptr())))
+        sdw = n.sdw
+        dzh = n.dz_h.data_ptr() if n.dz_h is not None else None
         pr = L.GemmProblem(a_kcontig=0, b_kcontig=0, M=n.N, N=n.K, K=M, splits=sdw,
                            A=n.dz.data_ptr(), lda=n.N, B=a_ptr, ldb=lda,
                            C=(n.dwslab if sdw > 1 else n.dW).data_ptr(), ldc=n.K,
                            slab_stride=n.N * n.K if sdw > 1 else 0)
         prh = self._h_variant(pr, dzh, None if self.qsrc[n.qkey]["Q"] else self._src_h(n))
-        out += [("dW %dx%dx%d%s" % (n.N, n.K, M, " s%d" % sdw if sdw > 1 else ""),
-                 2.0 * M * n.N * n.K, 4.0 * (M * n.N + M * n.K + sdw * n.N * n.K), pr,
-                 None if prh is None else (2.0 * (M * n.N + M * n.K) + 4.0 * sdw * n.N * n.K, prh))]
+        out += [Op("dW %dx%dx%d%s" % (n.N, n.K, M, " s%d" % sdw if sdw > 1 else ""),
+                   2.0 * M * n.N * n.K, 4.0 * (M * n.N + M * n.K + sdw * n.N * n.K), pr,
+                   None if prh is None else (2.0 * (M * n.N + M * n.K) + 4.0 * sdw * n.N * n.K, prh))]
         if n.src[0] == "fea" and self.want_dx:
             # external mode: dL/dx of the caller's input, one slab straight into ext_dx
             W = n.Wq if n.qbits else n.W
@@ -2755,8 +2216,8 @@ class Engine:
             kt = self._wt(n.W, True)
             if kt is not None:
                 pr.ktiles, pr.kmax = kt[0].data_ptr(), kt[1]
-            out.append(("dX %dx%dx%d ext" % (M, n.K, n.N), 2.0 * M * n.N * n.K,
-                        4.0 * (M * n.N + n.N * n.K + M * n.K), pr))
+            out.append(Op("dX %dx%dx%d ext" % (M, n.K, n.N), 2.0 * M * n.N * n.K,
+                          4.0 * (M * n.N + n.N * n.K + M * n.K), pr))
         if n.src[0] == "node" and self.needs_grad[n.src[1]]:
             P = n.src[1]
             off = P.cons_off[P.consumers.index(n)]
@@ -2777,10 +2238,10 @@ class Engine:
                     if q is not None:
                         q.C, q.X1 = P.dz.data_ptr(), C.addressof(P.bnb_epi)
                 P.bnb_now = True
-            out.append(("dX %dx%dx%d%s" % (M, n.K, n.N, " sparse %.2f" % d if kt is not None else ""),
-                        2.0 * M * n.N * n.K * d, 4.0 * (M * n.N + n.N * n.K * d + n.sx * M * n.K),
-                        pr, None if prh is None else
-                        (2.0 * (M * n.N + n.N * n.K * d) + 4.0 * n.sx * M * n.K, prh)))
+            out.append(Op("dX %dx%dx%d%s" % (M, n.K, n.N, " sparse %.2f" % d if kt is not None else ""),
+                          2.0 * M * n.N * n.K * d, 4.0 * (M * n.N + n.N * n.K * d + n.sx * M * n.K),
+                          pr, None if prh is None else
+                          (2.0 * (M * n.N + n.N * n.K * d) + 4.0 * n.sx * M * n.K, prh)))
         return out
 
     def _bnb_ok(self, P, n, pr, prh):
@@ -2790,14 +2251,14 @@ class Engine:
         if not (BN_BWD_EPI and self.M > 128 and not self.seq and P.bn and not P.ln and not P.head
                 and P.W is not None and len(P.consumers) == 1 and pr.splits == 1
                 and not P.mse_grad
-                and getattr(P, "bn_sums", None) is None and (P.drop == 0 or P.keep is not None)):
+                and P.bn_sums is None and (P.drop == 0 or P.keep is not None)):
             return False
         lib = L.lib()
         for prec, q in ((self.prec, pr), (L.PREC_BF16IN, prh)):
             if q is not None and lib.pkc_gemm_bnbwd_ok(prec, 1, 0, q.M, q.N, q.K, C.c_void_p(q.A),
                                                        q.lda, C.c_void_p(q.B), q.ldb) != 128:
                 return False
-        if getattr(P, "bnb_epi", None) is None:
+        if P.bnb_epi is None:
             P.bnb_epi = L.BnBwdEpi(xhat=P.xhat.data_ptr(),
                                    keep=P.keep.data_ptr() if P.keep is not None else None,
                                    gamma=P.gamma.data_ptr(), beta=P.beta.data_ptr(),
@@ -2806,29 +2267,20 @@ class Engine:
 
     def _dw_sum_op(self, n):
         """The slab sum of a split-K dW into the gradient (an operation of the next launch)."""
-        return ("dW slab-sum %s x%d" % (n.name, n.sdw), 0.0, 4.0 * n.N * n.K * (n.sdw + 1),
-                L.GemmProblem(kind=L.OP_SLABSUM, M=n.sdw, N=n.N * n.K, A=n.dwslab.data_ptr(),
-                              C=n.dW.data_ptr(), slab_stride=n.N * n.K))
-
-    def _dense_bwd(self, n, s):
-        self._dense_bwd_pre(n, s)
-        self._gemms(self._bwd_problems(n), s)
+        return Op("dW slab-sum %s x%d" % (n.name, n.sdw), 0.0, 4.0 * n.N * n.K * (n.sdw + 1),
+                  L.GemmProblem(kind=L.OP_SLABSUM, M=n.sdw, N=n.N * n.K, A=n.dwslab.data_ptr(),
+                                C=n.dW.data_ptr(), slab_stride=n.N * n.K))
 
     def _rec_bwd(self, n, s, want_dx0=False, on_layer=None):
         """BPTT of a recurrent node, top layer first; on_layer(li) after layer li's weight
         gradients are queued (the data-parallel bucket cut)."""
-        if getattr(n, "std", False):
+        if n.std:
             return self._std_bwd(n, s, want_dx0=want_dx0, on_layer=on_layer)
         M, T = self.M, self.T
-        gs = getattr(n, "gsrc", None)
-        if gs is not None:                   # external mode: the caller's output gradient
-            dy_t, dy_ns, dy_stride = gs[0], gs[1], gs[2]
-        else:
-            dy_t, dy_ns = n.gslab, n.sb
-            dy_stride = M * n.N
+        dy_t, dy_ns, dy_stride = self._out_grad(n)
         dy_ptr = dy_t.data_ptr()
         # tests: where each layer's dL/dy slabs sit (tests/test_gpu_steps.py re-reads them)
-        trace = getattr(self, "rec_dy_trace", None)
+        trace = self.rec_dy_trace
         for li in reversed(range(len(n.layers))):
             sp, lb = n.layers[li], n.lbuf[li]
             H, K = lb["H"], lb["K"]
@@ -2886,16 +2338,16 @@ class Engine:
                                            A=dz, lda=H, B=n.wq(li, "W", g).data_ptr(), ldb=K,
                                            C=lb["dx"].data_ptr() + 4 * nx * M * K, ldc=K,
                                            slab_stride=M * K, ktiles=kt[0].data_ptr(), kmax=kt[1])
-                        dxp.append(("dX%d %dx%dx%d sparse %.2f" % (g, M, K, H, kt[2]),
-                                    2.0 * M * H * K * kt[2], 4.0 * (M * H + H * K * kt[2] + M * K), pr))
+                        dxp.append(Op("dX%d %dx%dx%d sparse %.2f" % (g, M, K, H, kt[2]),
+                                      2.0 * M * H * K * kt[2], 4.0 * (M * H + H * K * kt[2] + M * K), pr))
                     else:
                         sx = _splits(M, K, H, MAX_SPLITS)
                         pr = L.GemmProblem(a_kcontig=1, b_kcontig=0, M=M, N=K, K=H, splits=sx,
                                            A=dz, lda=H, B=n.wq(li, "W", g).data_ptr(), ldb=K,
                                            C=lb["dx"].data_ptr() + 4 * nx * M * K, ldc=K,
                                            slab_stride=M * K)
-                        dxp.append(("dX%d %dx%dx%d" % (g, M, K, H), 2.0 * M * H * K,
-                                    4.0 * (M * H + H * K + sx * M * K), pr))
+                        dxp.append(Op("dX%d %dx%dx%d" % (g, M, K, H), 2.0 * M * H * K,
+                                      4.0 * (M * H + H * K + sx * M * K), pr))
                     nx += sx
             if dxp or sums:
                 self._gemms(dxp + sums, s)
@@ -2945,29 +2397,25 @@ class Engine:
             pr = L.GemmProblem(a_kcontig=0, b_kcontig=0, M=Mq, N=Nq, K=Kq, splits=ss, A=A,
                                lda=lda, B=B, ldb=ldb, C=dst, ldc=Nq,
                                slab_stride=Mq * Nq if ss > 1 else 0)
-            q = ("%s %dx%dx%d%s" % (lab, Mq, Nq, Kq, " s%d" % ss if ss > 1 else ""),
-                 2.0 * Mq * Nq * Kq, 4.0 * (Mq * Kq + Nq * Kq + ss * Mq * Nq), pr)
+            half = None
             if hq is not None:
                 ph = L.GemmProblem.from_buffer_copy(pr)
                 ph.A, ph.lda, ph.B, ph.ldb = hq
-                q = q + ((2.0 * (Mq * Kq + Nq * Kq) + 4.0 * ss * Mq * Nq, ph),)
-            gem.append(q)
+                half = (2.0 * (Mq * Kq + Nq * Kq) + 4.0 * ss * Mq * Nq, ph)
+            gem.append(Op("%s %dx%dx%d%s" % (lab, Mq, Nq, Kq, " s%d" % ss if ss > 1 else ""),
+                          2.0 * Mq * Nq * Kq, 4.0 * (Mq * Kq + Nq * Kq + ss * Mq * Nq), pr, half))
             if ss > 1:
-                sums.append(("rnn slab-sum %s x%d" % (lab, ss), 0.0, 4.0 * Mq * Nq * (ss + 1),
-                             L.GemmProblem(kind=L.OP_SLABSUM, M=ss, N=Mq * Nq, A=dst,
-                                           C=out.data_ptr(), slab_stride=Mq * Nq)))
+                sums.append(Op("rnn slab-sum %s x%d" % (lab, ss), 0.0, 4.0 * Mq * Nq * (ss + 1),
+                               L.GemmProblem(kind=L.OP_SLABSUM, M=ss, N=Mq * Nq, A=dst,
+                                             C=out.data_ptr(), slab_stride=Mq * Nq)))
                 off += ss * Mq * Nq
         self._gemms(gem, s)
         return sums
 
-    def _rec_slab_sum(self, slab, ns, numel, out, s):
-        """out = sum of ns split-K slabs of a recurrent weight gradient (one grouped launch)."""
-        self._rec_slab_sum_ptr(slab.data_ptr(), ns, numel, numel, out, s)
-
     def _rec_slab_sum_ptr(self, a_ptr, ns, numel, stride, out, s):
-        self._gemms([("rnn slab-sum x%d" % ns, 0.0, 4.0 * numel * (ns + 1),
-                      L.GemmProblem(kind=L.OP_SLABSUM, M=ns, N=numel, A=a_ptr,
-                                    C=out.data_ptr(), slab_stride=stride))], s)
+        self._gemms([Op("rnn slab-sum x%d" % ns, 0.0, 4.0 * numel * (ns + 1),
+                        L.GemmProblem(kind=L.OP_SLABSUM, M=ns, N=numel, A=a_ptr,
+                                      C=out.data_ptr(), slab_stride=stride))], s)
 
     def _opt_op(self, n, parts=1):
         """The optimizer update of node n's parameters as operations of grouped launches: `parts`
@@ -2983,12 +2431,12 @@ class Engine:
         for k in range(parts):
             e = (nch * (k + 1)) // parts
             segs = self._opt_segs(cmap, b, e)
-            ops.append(("opt %s%s" % (n.name, "" if parts == 1 else " [%d/%d]" % (k + 1, parts)), 0.0,
-                        (20.0 * nparam + 2.0 * nbout) * (e - b) / nch,
-                        L.GemmProblem(kind=L.OP_OPTIM, M=e - b, A=self.opt_desc.data_ptr(),
-                                      B=cmap.data_ptr() + 8 * b,
-                                      X1=C.addressof(segs) if segs is not None else None,
-                                      N=len(segs) if segs is not None else 0)))
+            ops.append(Op("opt %s%s" % (n.name, "" if parts == 1 else " [%d/%d]" % (k + 1, parts)), 0.0,
+                          (20.0 * nparam + 2.0 * nbout) * (e - b) / nch,
+                          L.GemmProblem(kind=L.OP_OPTIM, M=e - b, A=self.opt_desc.data_ptr(),
+                                        B=cmap.data_ptr() + 8 * b,
+                                        X1=C.addressof(segs) if segs is not None else None,
+                                        N=len(segs) if segs is not None else 0)))
             b = e
         return ops
 
@@ -3058,7 +2506,7 @@ class Engine:
                 # flush, so sibling heads can share the cut node's launch: wait for the slowest of
                 # them (an unsplit cut head beside a split one would otherwise ship the split
                 # head's stale dW in the first bucket)
-                cut_wait = 1 if any(getattr(p, "sdw", 1) > 1 for p in pend_nodes) else 0
+                cut_wait = 1 if any(p.sdw > 1 for p in pend_nodes) else 0
                 cut_node = None
             if cut_wait == 0:
                 cut_wait = -1
@@ -3078,16 +2526,16 @@ class Engine:
                 continue
             if not n.head:
                 flush()
-            if getattr(n, "conv", False):
+            if n.conv:
                 self._conv_bwd(n, s)
-            elif getattr(n, "combine", False):
+            elif n.combine:
                 self._combine_bwd(n, s)
             else:
                 self._dense_bwd_pre(n, s)
             pend += self._bwd_problems(n)
             pend_nodes.append(n)
             lag = 1
-            if getattr(n, "sdw", 1) > 1 and n.W is not None:
+            if n.sdw > 1 and n.W is not None:
                 future[1].append(self._dw_sum_op(n))    # the launch after the dW's
                 lag = 2                                 # its update one launch later still
             if spread_opt:
@@ -3106,11 +2554,11 @@ class Engine:
         self.spread_tail = []
         cur, summed = [], set()
         for f in future:
-            if any(op[0].startswith("opt ") and op[0][4:].split(" ")[0] in summed for op in f):
+            if any(op.label.startswith("opt ") and op.label[4:].split(" ")[0] in summed for op in f):
                 self.spread_tail.append(cur)
                 cur, summed = [], set()
             cur = cur + f
-            summed |= {op[0].split(" ")[2] for op in f if op[0].startswith("dW slab-sum ")}
+            summed |= {op.label.split(" ")[2] for op in f if op.label.startswith("dW slab-sum ")}
         if cur:
             self.spread_tail.append(cur)
         if not spread_opt:
@@ -3165,7 +2613,7 @@ class Engine:
         spread_opt = spread_opt and not self.reg_terms
         self._reg_grad_kernels(s)
         if spread_opt:
-            if getattr(self, "fwd_opt", None):
+            if self.fwd_opt:
                 # fwd_defer: every update waits for the next step's forward (_place_fwd_opt)
                 for f in self.spread_tail:
                     self._gemms(f, s)
@@ -3174,7 +2622,7 @@ class Engine:
             tail, pend = self.spread_tail, None
             if (defer and DEFER_TAIL and tail and not self.prune_list and not self.seq
                     and self.loss_heads and len(tail[-1]) < 8
-                    and all(op[3].kind == L.OP_OPTIM for op in tail[-1])):
+                    and all(op.prob.kind == L.OP_OPTIM for op in tail[-1])):
                 tail, pend = tail[:-1], tail[-1]
             for f in tail:
                 self._gemms(f, s)
@@ -3593,296 +3041,3 @@ def torch_optimizer(params, o):
                                    centered=_b(o["opt_centered"]),
                                    weight_decay=float(o["opt_weight_decay"]))
     raise NotImplementedError("arch_opt=%s" % kind)
-
-
-def _input_norm_bufs(norms, max_rows, inp_dim, dev):
-    """Work buffers of the forward runners' input LayerNorm / BatchNorm (one set per norm)."""
-    return [dict(y=_f32(max_rows * inp_dim, dev), xh=_f32(max_rows * inp_dim, dev),
-                 st=_f32(2 * max_rows, dev), sm=_f32(inp_dim, dev), si=_f32(inp_dim, dev),
-                 work=_f32(L.lib().pkc_dense_work_size(max_rows, inp_dim), dev))
-            for _ in norms]
-
-
-def _run_input_norms(norms, nbufs, cur, cld, K0, M, train, s):
-    """ln0 then bn0 of a forward runner over the (M, K0) matrix at address cur (row stride cld);
-    returns the address of the normalised matrix (cur itself without norms)."""
-    for ns, nb in zip(norms, nbufs):
-        if cld != K0:
-            raise NotImplementedError("input normalisation of a strided feature stream")
-        if ns["kind"] == "ln":
-            call("pkc_layernorm_fwd", M, K0, 1, C.c_void_p(cur), 0, None, ptr(ns["gamma"]),
-                 ptr(ns["beta"]), C.c_float(1e-6), ptr(nb["y"]), ptr(nb["xh"]), ptr(nb["st"]), s)
-        else:
-            a = L.DenseFwdArgs(
-                M=M, N=K0, nslab=1, zslab=cur, slab_stride=0, bias=None,
-                norm=L.NORM_BN_TRAIN if train else L.NORM_BN_EVAL, gamma=ns["gamma"].data_ptr(),
-                beta=ns["beta"].data_ptr(), running_mean=ns["rm"].data_ptr(),
-                running_var=ns["rv"].data_ptr(), momentum=0.05, eps=1e-5,
-                save_mean=nb["sm"].data_ptr(), save_invstd=nb["si"].data_ptr(), act=0,
-                xhat=nb["xh"].data_ptr(), out=nb["y"].data_ptr(), count_n=0)
-            call("pkc_dense_fwd", C.byref(a), ptr(nb["work"]), s)
-        cur = nb["y"].data_ptr()
-    return cur
-
-
-class ModuleRunner:
-    """Forward of one MLP module on the pkc kernels for any row count <= max_rows (MLP.forward for
-    stand-alone calls, and the per-utterance forward of run_nn's forward mode)."""
-
-    def __init__(self, net, max_rows, inp_dim):
-        net.check_supported()
-        self.net, self.rows, self.dev = net, max_rows, next(net.parameters()).device
-        self.specs = net.layer_specs()
-        self.norms = net.input_norm_specs() if hasattr(net, "input_norm_specs") else []
-        self.nbufs = _input_norm_bufs(self.norms, max_rows, inp_dim, self.dev)
-        self.bufs = []
-        K = inp_dim
-        for sp in self.specs:
-            N = sp["out"]
-            b = dict(z=_f32(MAX_SPLITS * max_rows * N, self.dev), K=K, N=N,
-                     xhat=_f32(max_rows * N, self.dev), sm=_f32(N, self.dev),
-                     si=_f32(N, self.dev), out=_f32(max_rows * N, self.dev),
-                     work=_f32(L.lib().pkc_dense_work_size(max_rows, N), self.dev))
-            if sp["ln"]:
-                b.update(ly=_f32(max_rows * N, self.dev), lxh=_f32(max_rows * N, self.dev),
-                         lst=_f32(2 * max_rows, self.dev))
-            if sp["quant"]:
-                b["Wq"] = torch.zeros_like(sp["W"])
-            if sp["inp_quant"]:
-                b["xq"] = _f32(max_rows * K, self.dev)
-                b["qwork"] = _f32(256, self.dev)
-            self.bufs.append(b)
-            K = N
-        self.prune_work = None
-        self.eff = pattern_effective_masks(net, Engine._stream())
-        # the reference re-prunes / re-applies pattern^L on every forward call
-        self.prunes = any(sp.get("prune") is not None for sp in self.specs) or bool(self.eff)
-        if not self.prunes:          # else refreshed at the top of every run()
-            self.refresh()
-
-    def refresh(self):
-        """Re-apply HCGS masks / the QuantizeLinear clamp and re-quantise (after weights change)."""
-        s = Engine._stream()
-        for sp, b in zip(self.specs, self.bufs):
-            qb = int(sp["quant"] or 0)
-            mask = self.eff.get(id(sp["W"]), sp["mask"])
-            if sp.get("prune") is not None:      # mask, then prune (neural_networks.py:256-278)
-                if mask is not None:
-                    call("pkc_apply_mask", ptr(sp["W"]), ptr(mask), sp["W"].numel(),
-                         C.c_float(0.0), s)
-                if self.prune_work is None:
-                    self.prune_work = torch.zeros(L.lib().pkc_prune_work_size(), dtype=torch.uint8,
-                                                  device=self.dev)
-                call("pkc_prune", ptr(sp["W"]), sp["W"].numel(), C.c_double(float(sp["prune"])), None,
-                     ptr(self.prune_work), s)
-                if qb:
-                    call("pkc_apply_mask", ptr(sp["W"]), None, sp["W"].numel(), C.c_float(1.0), s)
-            elif mask is not None or qb:
-                call("pkc_apply_mask", ptr(sp["W"]), ptr(mask), sp["W"].numel(),
-                     C.c_float(1.0 if qb else 0.0), s)
-            if qb:
-                call("pkc_fakequant_weight", ptr(sp["W"]), ptr(b["Wq"]), sp["W"].numel(), qb, s)
-
-    def run(self, x_ptr, ld, M, train=False, log_prior=None):
-        """x_ptr: device address of an (M, ld) fp32 matrix; returns the (M, N) output view.
-        With input quantisation on the first layer, self.input_version holds the address of the
-        quantised input (the value the reference leaves in the caller's tensor)."""
-        assert M <= self.rows
-        if self.prunes:
-            self.refresh()
-        s = Engine._stream()
-        cur, cld = x_ptr, ld
-        self.input_version = None
-        cur = _run_input_norms(self.norms, self.nbufs, cur, cld, self.bufs[0]["K"], M, train, s)
-        for li, (sp, b) in enumerate(zip(self.specs, self.bufs)):
-            N, K = b["N"], b["K"]
-            if sp["inp_quant"]:
-                if cld != K:
-                    raise NotImplementedError("input quantisation of a strided feature stream")
-                call("pkc_fakequant_input", C.c_void_p(cur), ptr(b["xq"]), M * K,
-                     int(sp["inp_quant"]), 1, ptr(b["qwork"]), s)
-                cur = b["xq"].data_ptr()
-                if li == 0:
-                    self.input_version = cur
-            W = b["Wq"] if sp["quant"] else sp["W"]
-            sf = _splits(M, N, K, MAX_SPLITS)
-            call("pkc_gemm", L.PREC_FP32, 1, 1, M, N, K, C.c_void_p(cur), cld, ptr(W), K,
-                 ptr(b["z"]), N, sf, M * N, s)
-            zp, zs, bias = b["z"].data_ptr(), M * N, sp["b"].data_ptr()
-            if sp["ln"]:
-                call("pkc_layernorm_fwd", M, N, sf, C.c_void_p(zp), zs, C.c_void_p(bias),
-                     ptr(sp["ln_gamma"]), ptr(sp["ln_beta"]), C.c_float(1e-6), ptr(b["ly"]),
-                     ptr(b["lxh"]), ptr(b["lst"]), s)
-                zp, zs, bias, sf = b["ly"].data_ptr(), 0, None, 1
-            if sp["act"] == "softmax":
-                a = L.NllArgs(M=M, N=N, nslab=sf, zslab=zp, slab_stride=zs,
-                              bias=bias, labels=None, label_stride=0, weight=0.0,
-                              logp=b["out"].data_ptr(),
-                              log_prior=log_prior.data_ptr() if log_prior is not None else None,
-                              dlogits=None, row_loss=None, row_err=None)
-                call("pkc_nll_fused", C.byref(a), s)
-            else:
-                a = L.DenseFwdArgs(
-                    M=M, N=N, nslab=sf, zslab=zp, slab_stride=zs, bias=bias,
-                    norm=(L.NORM_BN_TRAIN if train else L.NORM_BN_EVAL) if sp["bn"] else L.NORM_NONE,
-                    gamma=sp["gamma"].data_ptr(), beta=sp["beta"].data_ptr(),
-                    running_mean=sp["rm"].data_ptr(), running_var=sp["rv"].data_ptr(), momentum=0.05,
-                    eps=1e-5, save_mean=b["sm"].data_ptr(), save_invstd=b["si"].data_ptr(),
-                    act=L.ACT[sp["act"]], drop_p=0.0, seed=0, step_ctr=None, stream_id=0,
-                    keep_in=None, keep_out=None, xhat=b["xhat"].data_ptr(), out=b["out"].data_ptr(),
-                    count_n=0)
-                call("pkc_dense_fwd", C.byref(a), ptr(b["work"]), s)
-            cur, cld = b["out"].data_ptr(), N
-        return self.bufs[-1]["out"][:M * self.bufs[-1]["N"]].view(M, -1)
-
-    def forward(self, x, train=False):
-        x = x.contiguous().float()
-        return self.run(x.data_ptr(), x.shape[1], x.shape[0], train).clone()
-
-
-class ConvRunner:
-    """Forward of one CNN / SincNet module on the pkc kernels for any row count <= max_rows
-    (run_nn's forward mode): the ModuleRunner interface.  A sinc layer's filters are generated once
-    per call."""
-
-    def __init__(self, net, max_rows, inp_dim):
-        net.check_supported()
-        self.net, self.rows, self.dev = net, max_rows, next(net.parameters()).device
-        self.specs = net.conv_specs()
-        self.norms = net.input_norm_specs()
-        self.nbufs = _input_norm_bufs(self.norms, max_rows, inp_dim, self.dev)
-        self.inp_dim = inp_dim
-        self.bufs = []
-        for sp in self.specs:
-            if sp.get("sinc") is not None:
-                sinc_bind(sp)
-            N = sp["C_out"] * sp["L_out"]
-            self.bufs.append(dict(
-                N=N, z=_f32(max_rows * N, self.dev), out=_f32(max_rows * N, self.dev),
-                off=torch.zeros(max_rows * N, dtype=torch.uint8, device=self.dev),
-                xhat=_f32(max_rows * N, self.dev), sm=_f32(sp["C_out"], self.dev),
-                si=_f32(sp["C_out"], self.dev), st=_f32(2 * max_rows * sp["C_out"], self.dev)))
-        self.input_version = None
-
-    def run(self, x_ptr, ld, M, train=False, log_prior=None):
-        assert M <= self.rows
-        s = Engine._stream()
-        cur, cld = x_ptr, ld
-        cur = _run_input_norms(self.norms, self.nbufs, cur, cld, self.inp_dim, M, train, s)
-        for sp, b in zip(self.specs, self.bufs):
-            if sp.get("sinc") is not None:          # the filters of the current parameters
-                call("pkc_sinc_filters_fwd", C.byref(sinc_args(sp)), s)
-            a = conv_args(sp, M, cur, cld, b["z"], b["off"])
-            call("pkc_conv1d_fwd", C.byref(a), s)
-            pa = conv_post_args(sp, M, b["z"], train, b["out"], save_mean=b["sm"].data_ptr(),
-                                save_invstd=b["si"].data_ptr(), ln_stat=b["st"].data_ptr(),
-                                drop_p=0.0, xhat=b["xhat"].data_ptr())
-            call("pkc_conv_post_fwd", C.byref(pa), s)
-            cur, cld = b["out"].data_ptr(), b["N"]
-        return self.bufs[-1]["out"][:M * self.bufs[-1]["N"]].view(M, -1)
-
-    def forward(self, x, train=False):
-        x = x.contiguous().float()
-        return self.run(x.data_ptr(), x.shape[1], x.shape[0], train).clone()
-
-
-class ForwardRunner:
-    """run_nn forward mode (core.py:134-145, 234-249) for feed-forward models: one utterance per
-    batch, BatchNorm with running statistics, no dropout, posteriors normalised by the log prior.
-    The [model] tensor operations (utils.py:2014-2043) run as one pkc_combine_fwd per line; the
-    prior of a combine output, and of a head that also feeds a combine, is subtracted on the host
-    (core.py:242-245), so the combine reads the head's unnormalised log posteriors."""
-
-    def __init__(self, nets, lines, fea_cols, forward_outs, max_rows=4096):
-        fea_cols = resolve_concat(lines, fea_cols)
-        self.lines, self.fea_cols, self.outs = lines, fea_cols, forward_outs
-        self.nets = nets
-        self.max_rows = max_rows
-        self.runners = {}
-        dims = {k: c1 - c0 for k, (c0, c1) in fea_cols.items()}
-        self.combine = {}                      # out -> (op, operand names, constant, N, buffer)
-        self.tensor_inputs = set()
-        for out, op, a, b in lines:
-            if op == "compute":
-                runner = ConvRunner if hasattr(nets[a], "conv_specs") else ModuleRunner
-                self.runners[a] = runner(nets[a], max_rows, dims[b])
-                dims[out] = nets[a].out_dim
-            elif op in TENSOR_OPS and out not in fea_cols and a in dims:
-                if a in fea_cols and op != "concatenate":
-                    raise NotImplementedError(
-                        "%s=%s(%s,%s): a feature stream as the first argument of %s is not on "
-                        "the pkc path (utils.py:1827-1828, 1907-1920)" % (out, op, a, b, op))
-                const = op in ("sum_constant", "mult_constant")
-                names = (a,) if const else (a, b)
-                if not const and b not in dims:
-                    raise ValueError("input %s of %s=%s is neither a feature nor a produced "
-                                     "output" % (b, out, op))
-                if op != "concatenate" and not const and dims[a] != dims[b]:
-                    raise NotImplementedError("%s=%s: operands %d and %d wide (only concatenate "
-                                              "takes unequal widths)" % (out, op, dims[a], dims[b]))
-                dims[out] = dims[a] + dims[b] if op == "concatenate" else dims[a]
-                dev = next(next(iter(nets.values())).parameters()).device
-                self.combine[out] = (op, names, float(b) if const else 0.0, dims[out],
-                                     _f32(max_rows * dims[out], dev))
-                self.tensor_inputs.update(names)
-        self.priors_dev = {}
-
-    def forward(self, feats, beg, end, priors):
-        M = end - beg
-        if M > self.max_rows:
-            raise ValueError("utterance of %d frames exceeds the forward buffer" % M)
-        produced, res, cur = {}, {}, {}
-        for out, op, a, b in self.lines:
-            if out in self.combine:
-                op, names, c, N, buf = self.combine[out]
-                ops = []
-                for name in names:
-                    if name in cur:
-                        raise NotImplementedError("%s: an operand of a combine operation under "
-                                                  "in-place input quantisation" % name)
-                    if name in self.fea_cols:
-                        c0, c1 = self.fea_cols[name]
-                        ops.append((feats.data_ptr() + 4 * (beg * feats.stride(0) + c0),
-                                    feats.stride(0), c1 - c0))
-                    else:
-                        ops.append((produced[name].data_ptr(), produced[name].shape[1],
-                                    produced[name].shape[1]))
-                ca = L.CombineArgs(op=L.COMBINE[op], M=M, Na=ops[0][2],
-                                   Nb=ops[1][2] if len(ops) > 1 else 0, a=ops[0][0], lda=ops[0][1],
-                                   b=ops[1][0] if len(ops) > 1 else None,
-                                   ldb=ops[1][1] if len(ops) > 1 else 0, c=c, out=buf.data_ptr())
-                call("pkc_combine_fwd", C.byref(ca), Engine._stream())
-                produced[out] = buf[:M * N].view(M, N)
-                if out in self.outs:
-                    res[out] = produced[out].cpu().numpy()
-                    if out in priors:              # core.py:242-245, host side as there
-                        res[out] = res[out] - priors[out]
-                if all(o in res for o in self.outs):
-                    break
-                continue
-            if op != "compute":
-                continue
-            if b in cur:                       # the version an earlier consumer quantised in place
-                xp, ld = cur[b]
-            elif b in self.fea_cols:
-                c0, _ = self.fea_cols[b]
-                xp, ld = feats.data_ptr() + 4 * (beg * feats.stride(0) + c0), feats.stride(0)
-            else:
-                xp, ld = produced[b].data_ptr(), produced[b].shape[1]
-            lp = None
-            host_prior = out in self.tensor_inputs     # a combine reads the unnormalised head
-            if out in self.outs and out in priors and not host_prior:
-                if out not in self.priors_dev:
-                    self.priors_dev[out] = torch.from_numpy(priors[out]).to(feats.device)
-                lp = self.priors_dev[out]
-            y = self.runners[a].run(xp, ld, M, train=False, log_prior=lp)
-            if self.runners[a].input_version is not None:
-                cur[b] = (self.runners[a].input_version, ld)
-            produced[out] = y
-            if out in self.outs:
-                res[out] = y.cpu().numpy()
-                if host_prior and out in priors:
-                    res[out] = res[out] - priors[out]
-            if all(o in res for o in self.outs):
-                break
-        return res

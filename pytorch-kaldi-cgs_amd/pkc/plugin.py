@@ -152,8 +152,7 @@ class ArchRunner:
             first = e.nodes[0]
             # an input normalisation in front writes dL/dx itself; matmul, conv and recurrent
             # first nodes write it into ext_dx
-            src = first.dz if (not first.rec and first.W is None
-                               and not getattr(first, "conv", False)) else e.ext_dx
+            src = first.dz if (not first.rec and first.W is None and not first.conv) else e.ext_dx
             dx = src[:M * e.F].view(M, e.F).clone()
         return dx, grads
 

@@ -26,7 +26,7 @@ def main():
     orig = Engine._gemms
 
     def rec(self, probs, s):
-        launches.append([tuple(q) for q in probs])
+        launches.append(list(probs))
         return orig(self, probs, s)
 
     Engine._gemms = rec
@@ -59,14 +59,14 @@ def main():
     for i, ops in enumerate(launches):
         if len(ops) < 2:
             continue
-        labels = [q[0] for q in ops]
-        gem = [q for q in ops if q[3].kind == L.OP_GEMM]
-        dx = [q for q in gem if q[0].startswith("dX")]
-        rest = [q for q in ops if q[3].kind != L.OP_GEMM]
+        labels = [q.label for q in ops]
+        gem = [q for q in ops if q.prob.kind == L.OP_GEMM]
+        dx = [q for q in gem if q.label.startswith("dX")]
+        rest = [q for q in ops if q.prob.kind != L.OP_GEMM]
         row = {"all": t_us(ops), "matmuls": t_us(gem), "dX": t_us(dx),
                "non-matmul": t_us(rest)}
         for q in ops:
-            row[q[0][:28]] = t_us([q])
+            row[q.label[:28]] = t_us([q])
         print("launch %d [%s]" % (i, ", ".join(labels)), flush=True)
         print("   " + "  ".join("%s %.2f" % (k, v) for k, v in row.items()), flush=True)
 

@@ -334,7 +334,8 @@ def _post_rel(got, ref, prior):
 def test_forward_mode_posterior_ensemble():
     import model_ops_ref as MR
     from oracle.run import parse_model as oparse
-    from pkc.engine import Engine, ForwardRunner, parse_model
+    from pkc.engine import Engine, parse_model
+    from pkc.runners import ForwardRunner
     archs, dims = MC.ens_archs()
     nets, onets, seq = build_nets(archs, dims, train=False)
     rs = np.random.RandomState(9)

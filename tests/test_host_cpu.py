@@ -346,7 +346,7 @@ def test_forward_update_placement_respects_deadlines():
     step k+1's forward BEFORE the first launch that reads that node's parameters (the gather launch
     = key None, then one launch per matmul node; two heads reading the same tensor share one), at
     most 8 operations per launch, balanced by bytes.  Host logic only (mock nodes)."""
-    from pkc.engine import Engine
+    from pkc.engine import Engine, Op
 
     class NS:                         # hashable by identity, like the engine's node objects
         def __init__(self, **kw):
@@ -363,7 +363,7 @@ def test_forward_update_placement_respects_deadlines():
     ops = []
     for n in nodes:
         for part in range(2 if n in body else 3):
-            ops.append((n, ("opt %s [%d]" % (n.name, part), 0.0, 7e6 if n in body else 15e6, None)))
+            ops.append((n, Op("opt %s [%d]" % (n.name, part), 0.0, 7e6 if n in body else 15e6, None)))
     slots = Engine._place_fwd_opt(NS(nodes=nodes), ops)
     order = [None] + body + [heads[0]]
     seen = {}
