@@ -850,6 +850,44 @@ typedef struct {
 int pkc_kaldi_feats_ok(const pkc_kaldi_feats_args* a);
 int pkc_kaldi_feats(const pkc_kaldi_feats_args* a, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * splice-feats and transform-feats (the fea_opts stages of the fMLLR feature pipe; Kaldi's
+ * SpliceFrames of feat/feature-functions.cc and featbin/transform-feats.cc restated, parity
+ * unpinned against Kaldi itself).  Additive to ABI 9.
+ *
+ * in / src_row / utt_of_row / utt_beg / utt_end: the row maps of pkc_feat_frontend — output row r
+ * (of Nout) is source frame s = src_row[r] of utterance u = utt_of_row[r] (of n_utts), whose frames
+ * are [utt_beg[u], utt_end[u]) of the N x D matrix `in`.  Per row, with K = D * (L + R + 1):
+ *   spl[j*D + d] = in[clamp(s + j - L, utt_beg[u], utt_end[u] - 1)][d],  j = 0..L+R  (past first)
+ *   mats != NULL: out[r][o] = (sum_{k < K} A[o][k] * spl[k]) + A[o][K],  o < Dout, where A is
+ *     matrix utt_mat[u] (matrix 0 when utt_mat is NULL) of the n_mats row-major Dout x (K + affine)
+ *     matrices of `mats`; a linear matrix (affine == 0) has no offset column.  The offset is added
+ *     after the sum (AddMatMat, then AddVecToRows).
+ *   mats == NULL: out[r] = spl, copied bit for bit (Dout must be K).
+ * Products and sums are fp32 (each element one fused multiply-add chain over ascending k from 0,
+ * then one addition); there are no atomics and a row reads only its own utterance: equal inputs
+ * give equal bits, whatever the order of the rows and whatever else the call computes.
+ *
+ * tiles: n_tiles pairs {first output row, row count}; the rows of a tile are consecutive output
+ * rows that are consecutive frames of one utterance, at most pkc_feat_transform_tile(...) of them,
+ * and the tiles together cover the output rows to write.  One workgroup takes one tile: it stages
+ * the tile's frames with their context and the utterance's matrix in LDS, and writes a row's
+ * outputs as 16-byte stores when Dout % 4 == 0.  A tile that names rows outside 0..Nout-1, or an
+ * utterance or matrix out of range, is left unwritten.
+ *
+ * pkc_feat_transform_ok: 1 when the shape is supported (else 0 and a pkc_last_error() text):
+ * D >= 1, 0 <= L, R <= 64, K <= 4096, 1 <= Dout <= 512 with a transform, Dout == K without.
+ * pkc_feat_transform_tile: the row count of a full tile for that shape (0 when unsupported).
+ * pkc_feat_transform returns PKC_ERR_UNSUPPORTED and launches nothing outside that range, and
+ * launches nothing for Nout == 0 or n_tiles == 0.
+ * ------------------------------------------------------------------------------------------- */
+int pkc_feat_transform_ok(int D, int L, int R, int Dout, int has_mat);
+int pkc_feat_transform_tile(int D, int L, int R, int Dout, int has_mat);
+int pkc_feat_transform(const float* in, int D, int L, int R, int64_t Nout, const int32_t* src_row,
+                       const int32_t* utt_of_row, const int32_t* utt_beg, const int32_t* utt_end,
+                       int n_utts, const int32_t* utt_mat, const float* mats, int n_mats, int Dout,
+                       int affine, const int32_t* tiles, int n_tiles, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

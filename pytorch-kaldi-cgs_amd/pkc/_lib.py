@@ -251,7 +251,11 @@ _SIGS = {
     "pkc_wav_frames": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "pkc_kaldi_feats_ok": (C.c_int, [C.POINTER(KaldiFeatsArgs)]),
     "pkc_kaldi_feats": (C.c_int, [C.POINTER(KaldiFeatsArgs), vp]),
-    "pkc_ark_write_mat": (C.c_int, [C.c_char_p, C.c_int, C.c_char_p, i64, i64, vp]),
+    "pkc_feat_transform_ok": (C.c_int, [C.c_int] * 5),
+    "pkc_feat_transform_tile": (C.c_int, [C.c_int] * 5),
+    "pkc_feat_transform": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, vp, vp, vp, vp, C.c_int, vp,
+                                     vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
+    "pkc_ark_write_mat":(C.c_int, [C.c_char_p, C.c_int, C.c_char_p, i64, i64, vp]),
     "pkc_ark_index": (i64, [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i64,
                             C.c_char_p, i64]),
     "pkc_ark_read_rows": (C.c_int, [C.c_char_p, i64, i64, i64, vp]),

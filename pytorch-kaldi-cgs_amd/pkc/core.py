@@ -71,8 +71,11 @@ def _read_features(fea_scp, fea_opts, output_folder):
     ``apply-cmvn ... | add-deltas ...`` fea_opts pipe (every shipped cfg) is parsed into a
     pkc.frontend.FeaFrontend that pkc_feat_frontend applies on the GPU after the upload; a
     ``pkc-wav-frames`` stage makes fea_scp a wav list whose signals are framed on the GPU, a leading
-    ``pkc-fbank`` / ``pkc-mfcc`` stage one whose fbank / MFCC features are computed there; any other
-    pipe is run through Kaldi exactly as the reference does.  Returns (feats, frontend or None)."""
+    ``pkc-fbank`` / ``pkc-mfcc`` stage one whose fbank / MFCC features are computed there;
+    ``splice-feats`` / ``transform-feats`` stages (the fMLLR pipe of make_fmllr_feats.sh) and further
+    apply-cmvn / add-deltas groups run there too, as pkc_feat_transform / pkc_feat_frontend
+    launches; any other pipe is run through Kaldi exactly as the reference does.
+    Returns (feats, frontend or None)."""
     if fea_opts.strip() and not FE.is_native_pipe(fea_opts):
         import subprocess
         cmd = "copy-feats scp:" + fea_scp + " ark:- |" + fea_opts

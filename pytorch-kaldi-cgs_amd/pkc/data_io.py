@@ -317,7 +317,9 @@ class StagedChunk:
 
     With a Kaldi front-end (pkc.frontend.FeaFrontend: apply-cmvn / add-deltas), whole utterances
     are uploaded in their own order and pkc_feat_frontend writes the processed frames in the
-    sorted / split order on the same stream.
+    sorted / split order on the same stream.  A longer pipe (splice-feats / transform-feats,
+    further apply-cmvn / add-deltas groups) is a chain of pkc_feat_frontend / pkc_feat_transform
+    launches there (pipe_maps): all but the last write whole utterances, the last one sorts.
 
     With a wav-list stream (pkc.frontend.WavFrames) the upload is the utterances' int16 samples
     and pkc_wav_frames cuts the (N, W) matrix of overlapping windows from them, on that stream.
@@ -355,13 +357,17 @@ class StagedChunk:
                     nk = len(kf_args["pinned"])
                     self._kf_inputs = dev_t[:nk]
                     dev_t = [kaldi_feats_device(dev_t[:nk], kf_args["kf"], self.stream)] + dev_t[nk:]
-                raw_src, srow, urow, ubeg, uend, unorm, norm, scales = dev_t
-                Nout, Dout = fe_args["out_shape"]
-                self.raw_d = torch.empty(Nout, Dout, dtype=torch.float32, device=dev)
-                call("pkc_feat_frontend", ptr(raw_src), int(fe_args["D"]), Nout, ptr(srow),
-                     ptr(urow), ptr(ubeg), ptr(uend), ptr(unorm), ptr(norm), fe_args["cmvn_mode"],
-                     ptr(scales), fe_args["order"], fe_args["maxoff"], ptr(self.raw_d),
-                     C.c_void_p(self.stream.cuda_stream))
+                if "launches" in fe_args:       # pipe_maps: a pipe of several launches
+                    self.raw_d, mids = feat_pipe_device(dev_t[0], dev_t[1:], fe_args, self.stream)
+                    dev_t = dev_t + mids
+                else:
+                    raw_src, srow, urow, ubeg, uend, unorm, norm, scales = dev_t
+                    Nout, Dout = fe_args["out_shape"]
+                    self.raw_d = torch.empty(Nout, Dout, dtype=torch.float32, device=dev)
+                    call("pkc_feat_frontend", ptr(raw_src), int(fe_args["D"]), Nout, ptr(srow),
+                         ptr(urow), ptr(ubeg), ptr(uend), ptr(unorm), ptr(norm),
+                         fe_args["cmvn_mode"], ptr(scales), fe_args["order"], fe_args["maxoff"],
+                         ptr(self.raw_d), C.c_void_p(self.stream.cuda_stream))
                 self._dev_inputs = dev_t
             self.done = torch.cuda.Event()
             self.done.record(self.stream)
@@ -383,7 +389,11 @@ def frontend_args(fea, pieces, frontend):
 def frontend_maps(n_frames, D, pieces, frontend):
     """frontend_args without the frames themselves: n_frames {utt: frame count}, D their width.
     `keys` names the utterances in the order their frames must lie in pkc_feat_frontend's raw."""
-    from .frontend import delta_scales
+    from .frontend import CmvnDeltas, delta_scales
+    groups = frontend.groups()
+    if len(groups) != 1 or not isinstance(groups[0], CmvnDeltas):
+        return pipe_maps(n_frames, D, pieces, groups)
+    frontend = groups[0]
     keys = list(dict.fromkeys(k for k, _, _ in pieces))
     if not keys:
         raise ValueError("empty chunk: no utterance survived the feature / label / cmvn filters")
@@ -405,6 +415,101 @@ def frontend_maps(n_frames, D, pieces, frontend):
               nidx.astype(np.int32), norm.astype(np.float32), scales.astype(np.float32)]
     return dict(keys=keys, D=D, arrays=arrays, cmvn_mode=mode, order=frontend.order, maxoff=maxoff,
                 out_shape=(len(srow), frontend.out_dim(D)))
+
+
+def feat_tiles(srow, urow, tile_rows):
+    """The tile table of pkc_feat_transform for the row maps srow / urow: (n_tiles, 2) int32
+    {first output row, row count}, every tile a run of at most tile_rows consecutive output rows
+    that are consecutive frames of one utterance."""
+    n = len(srow)
+    if n == 0:
+        return np.zeros((0, 2), np.int32)
+    brk = np.flatnonzero((np.diff(urow) != 0) | (np.diff(srow) != 1)) + 1
+    starts, ends = np.concatenate([[0], brk]), np.concatenate([brk, [n]])
+    nt = -(-(ends - starts) // tile_rows)
+    nth = np.arange(nt.sum()) - np.repeat(np.cumsum(nt) - nt, nt)     # a tile's number in its run
+    first = np.repeat(starts, nt) + nth * tile_rows
+    count = np.minimum(tile_rows, np.repeat(ends, nt) - first)
+    return np.stack([first, count], 1).astype(np.int32)
+
+
+def pipe_maps(n_frames, D, pieces, groups):
+    """frontend_maps for a pipe of several launches (pkc.frontend.FeaFrontend.groups): every launch
+    but the last writes whole utterances in upload order (identity row maps), the last one the
+    sorted / split order of `pieces`.  arrays: the identity maps, the final maps and the utterance
+    ranges, then three tables per launch — pkc_feat_frontend: cmvn index, cmvn tables, delta
+    windows; pkc_feat_transform: matrix index, matrices, tile table — which `launches` describes."""
+    from .frontend import CmvnDeltas, delta_scales
+    keys = list(dict.fromkeys(k for k, _, _ in pieces))
+    if not keys:
+        raise ValueError("empty chunk: no utterance survived the feature / label / cmvn / "
+                         "transform filters")
+    uid = {k: i for i, k in enumerate(keys)}
+    lens = np.array([n_frames[k] for k in keys], dtype=np.int64)
+    ubeg = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    total = int(lens.sum())
+    if total >= 2 ** 31:
+        raise ValueError("chunk too large for the int32 front-end row maps")
+    maps = [np.arange(total, dtype=np.int32), np.repeat(np.arange(len(keys)), lens).astype(np.int32),
+            np.concatenate([np.arange(a, b) + ubeg[uid[k]] for k, a, b in pieces]).astype(np.int32),
+            np.concatenate([np.full(b - a, uid[k]) for k, a, b in pieces]).astype(np.int32)]
+    arrays = maps + [ubeg.astype(np.int32), (ubeg + lens).astype(np.int32)]
+    launches = []
+    for gi, g in enumerate(groups):
+        at = 2 if gi == len(groups) - 1 else 0
+        ln = dict(D=D, Dout=g.out_dim(D), rows=len(maps[at]), map=at, at=len(arrays))
+        if isinstance(g, CmvnDeltas):
+            kept, norm, nidx, mode = g.norm_tables(keys, D)
+            if kept != keys:
+                raise ValueError("utterances without cmvn statistics reached the front-end")
+            if mode == 0:
+                norm, nidx = np.zeros((1, 2, D), np.float32), np.zeros(len(keys), np.int32)
+            scales, maxoff = delta_scales(g.order, g.window)
+            ln.update(kind="frontend", cmvn_mode=mode, order=g.order, maxoff=maxoff)
+            arrays += [nidx.astype(np.int32), norm.astype(np.float32), scales.astype(np.float32)]
+        else:
+            has = g.transform is not None
+            if L.lib().pkc_feat_transform_ok(D, g.left, g.right, ln["Dout"], int(has)) != 1:
+                raise NotImplementedError("splice-feats / transform-feats not on the pkc path: %s"
+                                          % L.lib().pkc_last_error().decode())
+            tiles = feat_tiles(maps[at], maps[at + 1], L.lib().pkc_feat_transform_tile(
+                D, g.left, g.right, ln["Dout"], int(has)))
+            mats, midx = g.transform.tables(keys) if has else (np.zeros((0, 0, 0), np.float32),
+                                                               np.zeros(0, np.int32))
+            ln.update(kind="transform", left=g.left, right=g.right, n_mats=len(mats),
+                      affine=g.transform.shape(D * (g.left + g.right + 1))[1] if has else 0,
+                      n_tiles=len(tiles))
+            arrays += [midx, mats, tiles]
+        launches.append(ln)
+        D = ln["Dout"]
+    return dict(keys=keys, D=launches[0]["D"], arrays=arrays, launches=launches, n_utts=len(keys),
+                out_shape=(len(maps[2]), D))
+
+
+def feat_pipe_device(src, dev, fa, stream):
+    """The launches of pipe_maps on `stream` (the current one): src the (frames, D) device matrix
+    of whole utterances, dev the device copies of fa["arrays"].  Returns the last launch's output
+    and the tensors the launches read (to be kept until the stream has run them)."""
+    s = C.c_void_p(stream.cuda_stream)
+    ubeg, uend = dev[4], dev[5]
+    keep = []
+    for ln in fa["launches"]:
+        srow, urow = dev[ln["map"]], dev[ln["map"] + 1]
+        a, b, c = dev[ln["at"]:ln["at"] + 3]
+        out = torch.empty(ln["rows"], ln["Dout"], dtype=torch.float32, device=src.device)
+        if ln["kind"] == "frontend":
+            call("pkc_feat_frontend", ptr(src), ln["D"], ln["rows"], ptr(srow), ptr(urow), ptr(ubeg),
+                 ptr(uend), ptr(a), ptr(b), ln["cmvn_mode"], ptr(c), ln["order"], ln["maxoff"],
+                 ptr(out), s)
+        else:
+            has = ln["n_mats"] > 0
+            call("pkc_feat_transform", ptr(src), ln["D"], ln["left"], ln["right"], ln["rows"],
+                 ptr(srow), ptr(urow), ptr(ubeg), ptr(uend), fa["n_utts"], ptr(a) if has else None,
+                 ptr(b) if has else None, ln["n_mats"], ln["Dout"], ln["affine"], ptr(c),
+                 ln["n_tiles"], ptr(out), s)
+        keep.append(src)
+        src = out
+    return src, keep
 
 
 def wav_args(sig, pieces, wav):
@@ -535,8 +640,8 @@ def stage_chunk(fea, labs, max_sequence_length, device="cuda", frontend=None):
         # without a frame, apply-cmvn nothing for one without statistics
         kf = frontend.feats
         fea = {k: s for k, s in fea.items() if kf.n_frames(len(s)) > 0}
-        kept = set(frontend.norm_tables(sorted(fea), kf.D)[0])
-        lens = {k: kf.n_frames(len(s)) for k, s in fea.items() if k in kept}
+        kept = set(frontend.kept_keys(sorted(fea), kf.D))
+        lens ={k: kf.n_frames(len(s)) for k, s in fea.items() if k in kept}
         names, pieces, lab_arrays, end_index = dataset_pieces(lens, labs, max_sequence_length)
         fa = frontend_maps(lens, kf.D, pieces, frontend)
         return StagedChunk(names, None, lab_arrays, end_index, device, fe_args=fa,
@@ -552,10 +657,11 @@ def stage_chunk(fea, labs, max_sequence_length, device="cuda", frontend=None):
         names, raw, lab_arrays, end_index = load_dataset(fea, labs, max_sequence_length)
         return StagedChunk(names, np.ascontiguousarray(raw, dtype=np.float32), lab_arrays,
                            end_index, device)
-    # apply-cmvn writes nothing for utterances it has no statistics for: drop them before the
-    # label filter / sort / split of load_dataset
+    # apply-cmvn writes nothing for utterances it has no statistics for, transform-feats nothing
+    # for those without a transform: drop them before the label filter / sort / split of
+    # load_dataset
     D = next(iter(fea.values())).shape[1] if fea else 0
-    kept = set(frontend.norm_tables(sorted(fea), D)[0])
+    kept = set(frontend.kept_keys(sorted(fea), D))
     fea = {k: v for k, v in fea.items() if k in kept}
     names, pieces, lab_arrays, end_index = dataset_pieces({k: len(v) for k, v in fea.items()}, labs,
                                                           max_sequence_length)

@@ -23,6 +23,14 @@ fea_lst a wav list and cuts the raw-waveform frames of the reference's save_raw_
 compute-fbank-feats / compute-mfcc-feats run on the GPU (``KaldiFeats``, pkc_kaldi_feats in
 csrc/pkc_kaldi_feats.hip) and feed the apply-cmvn / add-deltas stages behind them.  The log-mel
 values are pinned to transformers.audio_utils, a third-party Kaldi-compatible implementation.
+
+``splice-feats`` and ``transform-feats`` complete the pipe of Kaldi's steps/nnet/make_fmllr_feats.sh
+(cmvn, splice, LDA+MLLT ``final.mat``, per-speaker fMLLR ``trans.*``): ``FeaFrontend.parse`` returns
+the ordered stage list, ``FeaFrontend.groups`` folds it into launches — each ``apply-cmvn
+[| add-deltas]`` one pkc_feat_frontend, each ``[splice-feats |] transform-feats`` or lone
+``splice-feats`` one pkc_feat_transform (csrc/pkc_feat_transform.hip) — and the matrices are read
+here (``Transform``).  Restated from Kaldi's published SpliceFrames and transform-feats.cc; parity
+unpinned against Kaldi itself, as the cmvn / delta stages are.
 """
 import os
 import re
@@ -57,9 +65,34 @@ def read_utt2spk(path):
     return m
 
 
-def parse_stats_ark(buf):
-    """CMVN statistics archive: binary (``\\0BDM ``/``\\0BFM ``) or text (``key [ ... ]``) matrices
-    -> {key: float64 (rows, cols)} (the double precision ApplyCmvn reads them in)."""
+def read_matrix(buf, pos=0, what="cmvn stats"):
+    """One Kaldi matrix at buf[pos:], binary (``\\0BDM `` / ``\\0BFM ``) or text (`` [ ... ]``)
+    -> (float64 (rows, cols), position behind it)."""
+    if buf[pos:pos + 2] == b"\0B":
+        hdr = buf[pos + 2:pos + 5]
+        dt = {b"DM ": "<f8", b"FM ": "<f4"}.get(hdr)
+        if dt is None:
+            raise ValueError("%s: unsupported matrix type %r" % (what, hdr))
+        rows = struct.unpack("<i", buf[pos + 6:pos + 10])[0]
+        cols = struct.unpack("<i", buf[pos + 11:pos + 15])[0]
+        pos += 15
+        nb = rows * cols * np.dtype(dt).itemsize
+        if rows < 0 or cols < 0 or pos + nb > len(buf):
+            raise ValueError("%s: truncated %d x %d matrix" % (what, rows, cols))
+        m = np.frombuffer(buf[pos:pos + nb], dtype=dt).reshape(rows, cols)
+        return m.astype(np.float64), pos + nb
+    if not buf[pos:pos + 64].lstrip().startswith(b"["):
+        raise ValueError("%s: neither a binary matrix nor a text one ('[')" % what)
+    end = buf.index(b"]", pos)
+    body = buf[pos:end].decode("latin1").replace("[", " ").strip()
+    rows = [list(map(float, r.split())) for r in body.split("\n") if r.strip()]
+    return np.array(rows, dtype=np.float64).reshape(len(rows), -1), end + 1
+
+
+def parse_stats_ark(buf, what="cmvn stats"):
+    """Archive of matrices — the CMVN statistics, a table of transforms — binary (``\\0BDM `` /
+    ``\\0BFM ``) or text (``key [ ... ]``) -> {key: float64 (rows, cols)} (the double precision
+    ApplyCmvn reads its statistics in)."""
     out, pos = {}, 0
     n = len(buf)
     while pos < n:
@@ -69,24 +102,7 @@ def parse_stats_ark(buf):
             break
         sp = buf.index(b" ", pos)
         key = buf[pos:sp].decode("latin1")
-        pos = sp + 1
-        if buf[pos:pos + 2] == b"\0B":
-            hdr = buf[pos + 2:pos + 5]
-            dt = {b"DM ": "<f8", b"FM ": "<f4"}.get(hdr)
-            if dt is None:
-                raise ValueError("cmvn stats: unsupported matrix type %r" % hdr)
-            rows = struct.unpack("<i", buf[pos + 6:pos + 10])[0]
-            cols = struct.unpack("<i", buf[pos + 11:pos + 15])[0]
-            pos += 15
-            nb = rows * cols * np.dtype(dt).itemsize
-            out[key] = np.frombuffer(buf[pos:pos + nb], dtype=dt).reshape(rows, cols).astype(np.float64)
-            pos += nb
-        else:
-            end = buf.index(b"]", pos)
-            body = buf[pos:end].decode("latin1").replace("[", " ").strip()
-            rows = [list(map(float, r.split())) for r in body.split("\n") if r.strip()]
-            out[key] = np.array(rows, dtype=np.float64)
-            pos = end + 1
+        out[key], pos = read_matrix(buf, sp + 1, what)
     return out
 
 
@@ -448,26 +464,189 @@ def read_wav_list(path):
     return out
 
 
+def split_pipe(fea_opts):
+    """The stages of a fea_opts pipe: cut at every ``|`` outside quotes (a quoted rspecifier such as
+    ``"ark:cat trans.* |"`` stays inside its stage)."""
+    out, cur, quote = [], [], None
+    for ch in fea_opts:
+        if quote:
+            quote = None if ch == quote else quote
+        elif ch in "'\"":
+            quote = ch
+        elif ch == "|":
+            out.append("".join(cur))
+            cur = []
+            continue
+        cur.append(ch)
+    out.append("".join(cur))
+    return [s.strip() for s in out if s.strip()]
+
+
+class Transform:
+    """The <transform> of one transform-feats stage: one matrix for every utterance (`mats` holds
+    it under the key None), or a table keyed by speaker (with utt2spk) or by utterance.  Matrices
+    are float32 (Kaldi reads them as Matrix<BaseFloat>), all of one shape; a matrix as wide as the
+    features is linear, one column wider affine (its last column the offset)."""
+
+    STAGE = "transform-feats"
+
+    def __init__(self, mats, utt2spk=None, name=""):
+        self.mats = {k: np.ascontiguousarray(m, dtype=np.float32) for k, m in mats.items()}
+        self.utt2spk, self.name = utt2spk, name
+        if not self.mats:
+            raise ValueError("%s %s: no transform in the table" % (self.STAGE, name))
+        shapes = {m.shape for m in self.mats.values()}
+        if len(shapes) != 1 or any(len(s) != 2 or 0 in s for s in shapes):
+            raise ValueError("%s %s: transforms of different or empty shapes %s"
+                             % (self.STAGE, name, sorted(shapes)))
+        self.rows, self.cols = next(iter(shapes))
+
+    @classmethod
+    def read(cls, spec, utt2spk=None):
+        """spec: a matrix file (binary FM / DM or text) or ``ark:FILE``, a table of them (binary or
+        text entries); utt2spk: the --utt2spk rspecifier or None."""
+        if spec.rstrip().endswith("|"):
+            raise NotImplementedError("%s: the piped rspecifier %r is not read; write the table to "
+                                      "a file first (cat trans.* > trans.ark)" % (cls.STAGE, spec))
+        if re.match(r"scp[,:]", spec):
+            raise NotImplementedError("%s: scp: tables are not read (got %r); use ark:FILE"
+                                      % (cls.STAGE, spec))
+        m = re.match(r"ark(,[a-z,]*)?:(.*)$", spec)
+        if m is None:
+            if utt2spk:             # transform-feats.cc: "--utt2spk option not compatible with
+                raise ValueError("%s: --utt2spk with the global transform %s"   # global transform"
+                                 % (cls.STAGE, spec))
+            with open(spec, "rb") as f:
+                return cls({None: read_matrix(f.read(), 0, cls.STAGE + " " + spec)[0]}, None, spec)
+        with open(m.group(2), "rb") as f:
+            mats = parse_stats_ark(f.read(), cls.STAGE + " " + spec)
+        return cls(mats, read_utt2spk(_rspec_path(utt2spk, "utt2spk")) if utt2spk else None, spec)
+
+    def shape(self, K):
+        """(Dout, affine) of the transform over K-dimensional features; another width raises."""
+        if self.cols not in (K, K + 1):
+            raise ValueError("%s %s: a transform of %d x %d does not fit features of dimension %d "
+                             "(a linear one has %d columns, an affine one %d)"
+                             % (self.STAGE, self.name, self.rows, self.cols, K, K, K + 1))
+        return self.rows, int(self.cols == K + 1)
+
+    def _key(self, utt):
+        if None in self.mats:
+            return None
+        return self.utt2spk.get(utt) if self.utt2spk is not None else utt
+
+    def has(self, utt):
+        """Whether the utterance has a transform (transform-feats skips it otherwise)."""
+        return self._key(utt) in self.mats
+
+    def tables(self, keys):
+        """(mats (n, Dout, cols) float32, matrix index per utterance) for the utterances keys."""
+        index, order = {}, []
+        for k in keys:
+            mk = self._key(k)
+            if mk not in self.mats:
+                raise ValueError("utterances without a transform reached the front-end")
+            if mk not in index:
+                index[mk] = len(index)
+            order.append(index[mk])
+        return np.stack([self.mats[k] for k in index]), np.asarray(order, np.int32)
+
+
+class CmvnDeltas:
+    """One ``apply-cmvn [| add-deltas]`` group (or a lone add-deltas): one pkc_feat_frontend launch."""
+
+    def __init__(self, cmvn, order, window):
+        self.cmvn, self.order, self.window = cmvn, order, window
+
+    def out_dim(self, D):
+        return D * (self.order + 1)
+
+    def kept(self, keys, D):
+        return self.norm_tables(keys, D)[0]
+
+    def norm_tables(self, keys, D):
+        """(kept keys, norm (n, 2, D) float32 {offset, scale}, norm index per kept key, cmvn_mode).
+        Utterances without statistics are dropped, as apply-cmvn drops them (it warns and writes
+        nothing for them)."""
+        if self.cmvn is None or not self.cmvn["norm_means"]:
+            return list(keys), np.zeros((0, 2, D), np.float32), np.zeros(len(keys), np.int32), 0
+        stats, u2s = self.cmvn["stats"], self.cmvn["utt2spk"]
+        kept, idx, spk_index, tabs = [], [], {}, []
+        for k in keys:
+            sk = u2s.get(k) if u2s is not None else k
+            if sk is None or sk not in stats:
+                continue
+            if sk not in spk_index:
+                st = stats[sk]
+                if st.shape[1] - 1 != D:
+                    raise ValueError("cmvn stats dimension %d != feature dimension %d"
+                                     % (st.shape[1] - 1, D))
+                off, sc = cmvn_norm(st, self.cmvn["norm_vars"])
+                spk_index[sk] = len(tabs)
+                tabs.append(np.stack([off, sc]))
+            kept.append(k)
+            idx.append(spk_index[sk])
+        norm = np.stack(tabs).astype(np.float32) if tabs else np.zeros((0, 2, D), np.float32)
+        return kept, norm, np.asarray(idx, np.int32), 2 if self.cmvn["norm_vars"] else 1
+
+
+class SpliceTransform:
+    """One ``[splice-feats |] transform-feats`` group, or a lone splice-feats (transform None): one
+    pkc_feat_transform launch."""
+
+    def __init__(self, left, right, transform):
+        self.left, self.right, self.transform = left, right, transform
+
+    def out_dim(self, D):
+        K = D * (self.left + self.right + 1)
+        return K if self.transform is None else self.transform.shape(K)[0]
+
+    def kept(self, keys, D):
+        """transform-feats writes nothing for an utterance without a transform."""
+        self.out_dim(D)
+        if self.transform is None:
+            return list(keys)
+        return [k for k in keys if self.transform.has(k)]
+
+
+MAX_STAGES = 8
+
+
 class FeaFrontend:
-    """apply-cmvn / add-deltas stages of one fea_opts pipe, behind an optional first pkc-fbank /
-    pkc-mfcc stage, or its one pkc-wav-frames stage."""
+    """The apply-cmvn / add-deltas / splice-feats / transform-feats stages of one fea_opts pipe,
+    behind an optional first pkc-fbank / pkc-mfcc stage, or its one pkc-wav-frames stage.
+
+    `stages` is the ordered list parse() read: ("apply-cmvn", cmvn dict), ("add-deltas", order,
+    window), ("splice-feats", left, right), ("transform-feats", Transform).  A front-end built by
+    hand has no list: its one launch is the apply-cmvn / add-deltas group of `cmvn`, `order` and
+    `window`, which parse() also fills in for a pipe that is one such group."""
 
     def __init__(self):
         self.cmvn = None          # dict(stats={key: (2, D+1) f64}, utt2spk={utt: spk} | None, vars)
         self.order, self.window = 0, 2
         self.wav = None           # WavFrames: fea_lst is a wav list
         self.feats = None         # KaldiFeats: fea_lst is a wav list, fbank / mfcc computed first
+        self.stages = None
 
     @staticmethod
     def parse(fea_opts):
-        """fea_opts -> FeaFrontend (None for an empty pipe).  Stages other than apply-cmvn and
-        add-deltas (and options Kaldi does not have) raise NotImplementedError; so does
-        pkc-wav-frames beside any other stage or with an option it does not have, and pkc-fbank /
-        pkc-mfcc anywhere but in front."""
+        """fea_opts -> FeaFrontend (None for an empty pipe).  Stages other than apply-cmvn,
+        add-deltas, splice-feats and transform-feats (and options or table forms that are not
+        computed) raise NotImplementedError; so do a ninth stage, a pipe of splice-feats alone
+        (only_splices: it keeps its earlier treatment), pkc-wav-frames beside any other
+        stage or with an option it does not have, and pkc-fbank / pkc-mfcc anywhere but in front."""
         fe = FeaFrontend()
-        stages = [s.strip() for s in fea_opts.split("|") if s.strip()]
+        stages = split_pipe(fea_opts)
         if not stages:
             return None
+        if only_splices(stages):
+            raise NotImplementedError("fea_opts: a pipe of splice-feats alone has no native pkc "
+                                      "implementation; splice-feats runs beside another native "
+                                      "stage (got %s)" % " | ".join(stages))
+        if len(stages) > MAX_STAGES:
+            raise NotImplementedError("fea_opts: a pipe of %d stages (at most %d are run): %s"
+                                      % (len(stages), MAX_STAGES, " | ".join(stages)))
+        fe.stages = []
         if len(stages) > 1 and any(s.split()[0] == WAV_STAGE for s in stages):
             raise NotImplementedError("fea_opts: %s frames a wav list and must be the only stage of "
                                       "the pipe (got %s)" % (WAV_STAGE, " | ".join(stages)))
@@ -496,8 +675,6 @@ class FeaFrontend:
                     raise NotImplementedError("%s %s: expected ark:- ark:-" % (prog, " ".join(pos)))
                 fe.feats = KaldiFeats.from_options(prog, kv)
             elif prog == "apply-cmvn":
-                if fe.cmvn is not None or fe.order:
-                    raise NotImplementedError("fea_opts: apply-cmvn after add-deltas / twice")
                 unknown = set(kv) - {"utt2spk", "norm-vars", "norm-means", "reverse"}
                 if unknown or _strtobool(kv.get("reverse", "false")):
                     raise NotImplementedError("apply-cmvn options %s" % sorted(kv))
@@ -511,49 +688,85 @@ class FeaFrontend:
                 u2s = kv.get("utt2spk")
                 with open(_rspec_path(pos[0], "apply-cmvn stats"), "rb") as f:
                     stats = parse_stats_ark(f.read())
-                fe.cmvn = dict(stats=stats, utt2spk=read_utt2spk(_rspec_path(u2s, "utt2spk"))
-                               if u2s else None, norm_vars=norm_vars, norm_means=norm_means)
+                fe.stages.append(("apply-cmvn", dict(
+                    stats=stats, utt2spk=read_utt2spk(_rspec_path(u2s, "utt2spk")) if u2s else None,
+                    norm_vars=norm_vars, norm_means=norm_means)))
             elif prog == "add-deltas":
                 unknown = set(kv) - {"delta-order", "delta-window"}
                 if unknown:
                     raise NotImplementedError("add-deltas options %s" % sorted(kv))
                 if pos != ["ark:-", "ark:-"]:
                     raise NotImplementedError("add-deltas %s" % " ".join(pos))
-                fe.order = int(kv.get("delta-order", "2"))
-                fe.window = int(kv.get("delta-window", "2"))
-                if fe.order > 7:
+                order = int(kv.get("delta-order", "2"))
+                if order > 7:
                     raise NotImplementedError("add-deltas --delta-order > 7")
+                fe.stages.append(("add-deltas", order, int(kv.get("delta-window", "2"))))
+            elif prog == "splice-feats":
+                unknown = set(kv) - {"left-context", "right-context"}
+                if unknown:
+                    raise NotImplementedError("splice-feats options %s" % sorted(unknown))
+                if pos != ["ark:-", "ark:-"]:
+                    raise NotImplementedError("splice-feats %s: expected ark:- ark:-" % " ".join(pos))
+                left, right = int(kv.get("left-context", "4")), int(kv.get("right-context", "4"))
+                if left < 0 or right < 0:
+                    raise ValueError("splice-feats: --left-context=%d --right-context=%d"
+                                     % (left, right))
+                fe.stages.append(("splice-feats", left, right))
+            elif prog == "transform-feats":
+                unknown = set(kv) - {"utt2spk"}
+                if unknown:
+                    raise NotImplementedError("transform-feats options %s" % sorted(unknown))
+                if len(pos) != 3 or pos[1:] != ["ark:-", "ark:-"]:
+                    raise NotImplementedError("transform-feats %s: expected <transform> ark:- ark:-"
+                                              % " ".join(pos))
+                fe.stages.append(("transform-feats", Transform.read(pos[0], kv.get("utt2spk"))))
             else:
                 raise NotImplementedError("fea_opts stage %r has no native pkc implementation" % prog)
+        groups = fe.groups()
+        if len(groups) == 1 and isinstance(groups[0], CmvnDeltas):
+            fe.cmvn, fe.order, fe.window = groups[0].cmvn, groups[0].order, groups[0].window
         return fe
 
+    def groups(self):
+        """The launches of the pipe, in order: CmvnDeltas / SpliceTransform.  A pipe without such
+        a stage (pkc-fbank alone, a front-end built by hand) is the one CmvnDeltas of `cmvn`,
+        `order` and `window`, which also sorts and splits the frames."""
+        st = self.stages or []
+        out, i = [], 0
+        while i < len(st):
+            nxt = st[i + 1] if i + 1 < len(st) else (None,)
+            if st[i][0] == "apply-cmvn":
+                pair = nxt[0] == "add-deltas"
+                out.append(CmvnDeltas(st[i][1], nxt[1] if pair else 0, nxt[2] if pair else 2))
+            elif st[i][0] == "add-deltas":
+                pair = False
+                out.append(CmvnDeltas(None, st[i][1], st[i][2]))
+            elif st[i][0] == "splice-feats":
+                pair = nxt[0] == "transform-feats"
+                out.append(SpliceTransform(st[i][1], st[i][2], nxt[1] if pair else None))
+            else:
+                pair = False
+                out.append(SpliceTransform(0, 0, st[i][1]))
+            i += 2 if pair else 1
+        return out or [CmvnDeltas(self.cmvn, self.order, self.window)]
+
     def out_dim(self, D):
-        return D * (self.order + 1)
+        for g in self.groups():
+            D = g.out_dim(D)
+        return D
+
+    def kept_keys(self, keys, D):
+        """The utterances of `keys` (D-dimensional) the pipe writes: apply-cmvn drops those without
+        statistics, transform-feats those without a transform."""
+        keys = list(keys)
+        for g in self.groups():
+            keys = g.kept(keys, D)
+            D = g.out_dim(D)
+        return keys
 
     def norm_tables(self, keys, D):
-        """(kept keys, norm (n, 2, D) float32 {offset, scale}, norm index per kept key, cmvn_mode).
-        Utterances without statistics are dropped, as apply-cmvn drops them (it warns and writes
-        nothing for them)."""
-        if self.cmvn is None or not self.cmvn["norm_means"]:
-            return list(keys), np.zeros((0, 2, D), np.float32), np.zeros(len(keys), np.int32), 0
-        stats, u2s = self.cmvn["stats"], self.cmvn["utt2spk"]
-        kept, idx, spk_index, tabs = [], [], {}, []
-        for k in keys:
-            sk = u2s.get(k) if u2s is not None else k
-            if sk is None or sk not in stats:
-                continue
-            if sk not in spk_index:
-                st = stats[sk]
-                if st.shape[1] - 1 != D:
-                    raise ValueError("cmvn stats dimension %d != feature dimension %d"
-                                     % (st.shape[1] - 1, D))
-                off, sc = cmvn_norm(st, self.cmvn["norm_vars"])
-                spk_index[sk] = len(tabs)
-                tabs.append(np.stack([off, sc]))
-            kept.append(k)
-            idx.append(spk_index[sk])
-        norm = np.stack(tabs).astype(np.float32) if tabs else np.zeros((0, 2, D), np.float32)
-        return kept, norm, np.asarray(idx, np.int32), 2 if self.cmvn["norm_vars"] else 1
+        """CmvnDeltas.norm_tables of the one apply-cmvn / add-deltas group of `cmvn`."""
+        return CmvnDeltas(self.cmvn, self.order, self.window).norm_tables(keys, D)
 
 
 def kaldi_on_path():
@@ -561,10 +774,20 @@ def kaldi_on_path():
                for d in os.environ.get("PATH", "").split(os.pathsep) if d)
 
 
-_PIPE_RE = re.compile(r"^\s*(apply-cmvn|add-deltas|pkc-wav-frames|pkc-fbank|pkc-mfcc)\b")
+_PIPE_RE = re.compile(r"^\s*(apply-cmvn|add-deltas|splice-feats|transform-feats|pkc-wav-frames|"
+                      r"pkc-fbank|pkc-mfcc)\b")
+
+
+def only_splices(stages):
+    """A pipe that is nothing but splice-feats.  Existing behaviour does not move: such a pipe was
+    Kaldi's before splice-feats ran here and still is (no recipe reads spliced features without a
+    transform behind them); splice-feats runs natively beside any other native stage."""
+    return bool(stages) and all(s.split()[0] == "splice-feats" for s in stages)
 
 
 def is_native_pipe(fea_opts):
-    """True when every stage of fea_opts is one pkc runs itself."""
-    stages = [s for s in fea_opts.split("|") if s.strip()]
-    return bool(stages) and all(_PIPE_RE.match(s) for s in stages)
+    """True when every stage of fea_opts is one pkc runs itself (and the pipe is not splice-feats
+    alone, see only_splices)."""
+    stages = split_pipe(fea_opts)
+    return (bool(stages) and all(_PIPE_RE.match(s) for s in stages)
+            and not only_splices(stages))

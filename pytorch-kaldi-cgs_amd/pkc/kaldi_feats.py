@@ -33,17 +33,15 @@ def write_stats_ark(path, stats):
                     + st.tobytes())
 
 
-def write_feats(wav_lst, kf, ark_out, scp_out, utt2spk=None, cmvn_out=None):
-    """Returns {utt: float32 (frames, D)} of what was written."""
+def write_matrices(mats, ark_out, scp_out, utt2spk=None, cmvn_out=None):
+    """mats: iterable of (utt, float32 (frames, D)) -> the ark, its scp and, with cmvn_out, the
+    compute-cmvn-stats archive per speaker of utt2spk (per utterance without it).  Returns
+    {utt: matrix} of what was written."""
     u2s = read_utt2spk(utt2spk) if utt2spk else None
     feats, by_spk = {}, {}
     open(ark_out, "wb").close()
     with open(scp_out, "w") as scp:
-        for utt, path in read_wav_list(wav_lst):
-            s = kf.read(utt, path)
-            if kf.n_frames(len(s)) == 0:
-                continue
-            m = D.kaldi_features({utt: s}, kf).cpu().numpy()
+        for utt, m in mats:
             off = os.path.getsize(ark_out) + len(utt.encode("latin1")) + 1
             D.write_mat_path(ark_out, m, utt, append=True)
             scp.write("%s %s:%d\n" % (utt, ark_out, off))
@@ -54,6 +52,16 @@ def write_feats(wav_lst, kf, ark_out, scp_out, utt2spk=None, cmvn_out=None):
     if cmvn_out:
         write_stats_ark(cmvn_out, {spk: cmvn_stats(ms) for spk, ms in by_spk.items()})
     return feats
+
+
+def write_feats(wav_lst, kf, ark_out, scp_out, utt2spk=None, cmvn_out=None):
+    """Returns {utt: float32 (frames, D)} of what was written."""
+    def mats():
+        for utt, path in read_wav_list(wav_lst):
+            s = kf.read(utt, path)
+            if kf.n_frames(len(s)) > 0:
+                yield utt, D.kaldi_features({utt: s}, kf).cpu().numpy()
+    return write_matrices(mats(), ark_out, scp_out, utt2spk, cmvn_out)
 
 
 def main(argv=None):
