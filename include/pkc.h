@@ -226,6 +226,15 @@ int pkc_dense_fwd_sync_apply(const pkc_dense_fwd_args* a, float* work, const flo
 int pkc_dense_bwd_stats(const pkc_dense_bwd_args* a, float* work, float* sums, void* stream);
 int pkc_dense_bwd_sync_apply(const pkc_dense_bwd_args* a, float* work, const float* sums,
                              int total_rows, void* stream);
+/* pkc_dense_fwd_sync_apply for several BatchNorms whose states share ONE gathered buffer (a
+ * recurrent layer's G gate BatchNorms: states[R][G][3N], one collective per layer instead of G):
+ * `states` points at rank 0's state of THIS BatchNorm and rank r's is rank_stride floats further
+ * (rank_stride >= 3N; G * 3N for the gate buffer).  a->count_n > 0 gives the rows BatchNorm1d sees
+ * of this rank's M (a shared-weight bidirectional layer normalises 2x duplicated rows: 2 * M); the
+ * unbiased running_var correction then runs over the merged GLOBAL count times count_n / M.
+ * count_n == 0: the merged count itself, as pkc_dense_fwd_sync_apply. */
+int pkc_dense_fwd_sync_apply_packed(const pkc_dense_fwd_args* a, float* work, const float* states,
+                                    int nranks, int64_t rank_stride, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused LogSoftmax + NLLLoss(mean) + error rate + d(loss)/d(logits) for one output head

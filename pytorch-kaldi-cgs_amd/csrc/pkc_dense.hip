@@ -196,14 +196,17 @@ __global__ __launch_bounds__(ET) void dense_bwd_finalize_kernel(pkc_dense_bwd_ar
 // SyncBN: the ranks' (n, mean, M2) column states merged in rank order (Chan), then the same
 // outputs as dense_finalize_kernel from the global statistics (running_var unbiased over the
 // global row count).  One thread per column.
+// rank_stride: floats between two ranks' states of this layer (3N, or a packed buffer's row of
+// several layers' states); nmul: the rows BatchNorm1d sees per row of the states' counts (2 for a
+// shared-weight bidirectional layer, whose duplicated rows change only the unbiased correction)
 __global__ void dense_sync_merge_kernel(pkc_dense_fwd_args a, float* part, const float* states,
-                                        int nranks) {
+                                        int nranks, int64_t rank_stride, float nmul) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= a.N) return;
   const int64_t N = a.N;
   float n = 0.f, mu = 0.f, M2 = 0.f;
   for (int r = 0; r < nranks; ++r) {
-    const float* st = states + (int64_t)r * 3 * N;
+    const float* st = states + (int64_t)r * rank_stride;
     const float nk = st[c];
     if (nk == 0.f) continue;
     const float nn = n + nk;
@@ -218,7 +221,8 @@ __global__ void dense_sync_merge_kernel(pkc_dense_fwd_args a, float* part, const
   fin[N + c] = var;
   a.save_mean[c] = mu;
   a.save_invstd[c] = 1.f / sqrtf(var + a.eps);
-  const float unb = n > 1.f ? var * n / (n - 1.f) : var;
+  const float cn = n * nmul;
+  const float unb = cn > 1.f ? var * cn / (cn - 1.f) : var;
   a.running_mean[c] = (1.f - a.momentum) * a.running_mean[c] + a.momentum * mu;
   a.running_var[c] = (1.f - a.momentum) * a.running_var[c] + a.momentum * unb;
 }
@@ -1163,20 +1167,42 @@ extern "C" int pkc_dense_fwd_stats(const pkc_dense_fwd_args* a, float* work, flo
   return PKC_OK;
 }
 
-extern "C" int pkc_dense_fwd_sync_apply(const pkc_dense_fwd_args* a, float* work,
-                                        const float* states, int nranks, void* stream) {
+static int sync_fwd_apply(const pkc_dense_fwd_args* a, float* work, const float* states, int nranks,
+                          int64_t rank_stride, float nmul, void* stream) {
   using namespace pkc;
-  int st = sync_fwd_check(a, work);
-  if (st) return st;
-  PKC_CHECK_ARG(states && nranks >= 1, "pkc_dense_fwd_sync_apply: states / nranks");
   hipLaunchKernelGGL(dense_sync_merge_kernel, dim3((a->N + 255) / 256), dim3(256), 0, S(stream), *a,
-                     work, states, nranks);
+                     work, states, nranks, rank_stride, nmul);
   dim3 grid((a->N + EC - 1) / EC, (a->M + ERB - 1) / ERB);
   const dim3 grid4((a->N + 4 * EC4 - 1) / (4 * EC4), (a->M + ERB - 1) / ERB);
   const bool v4 = v4_fwd(a) && (int64_t)grid4.x * grid4.y >= V4_MIN_WG;
   { if (v4) hipLaunchKernelGGL(dense_apply_v4_kernel, grid4, dim3(ET), 0, S(stream), *a, work, ERB, true); else hipLaunchKernelGGL(dense_apply_kernel, grid, dim3(ET), 0, S(stream), *a, work, ERB, true); }
   PKC_LAUNCH_CHECK("pkc_dense_fwd_sync_apply");
   return PKC_OK;
+}
+
+extern "C" int pkc_dense_fwd_sync_apply(const pkc_dense_fwd_args* a, float* work,
+                                        const float* states, int nranks, void* stream) {
+  int st = sync_fwd_check(a, work);
+  if (st) return st;
+  PKC_CHECK_ARG(states && nranks >= 1, "pkc_dense_fwd_sync_apply: states / nranks");
+  return sync_fwd_apply(a, work, states, nranks, 3 * (int64_t)a->N, 1.f, stream);
+}
+
+// the ranks' states of this BatchNorm at states + r * rank_stride (several BatchNorms' states packed
+// in one buffer, gathered by one collective); a->count_n > 0: the rows BatchNorm1d sees of this
+// rank's M (a shared-weight bidirectional layer: 2 M), scaling the global count the same way
+extern "C" int pkc_dense_fwd_sync_apply_packed(const pkc_dense_fwd_args* a, float* work,
+                                               const float* states, int nranks,
+                                               int64_t rank_stride, void* stream) {
+  int st = sync_fwd_check(a, work);
+  if (st) return st;
+  PKC_CHECK_ARG(states && nranks >= 1, "pkc_dense_fwd_sync_apply_packed: states / nranks");
+  PKC_CHECK_ARG(rank_stride >= 3 * (int64_t)a->N,
+                "pkc_dense_fwd_sync_apply_packed: rank_stride %lld < 3 N", (long long)rank_stride);
+  PKC_CHECK_ARG(a->count_n == 0 || a->count_n >= a->M,
+                "pkc_dense_fwd_sync_apply_packed: count_n < M");
+  const float nmul = a->count_n > 0 ? (float)a->count_n / (float)a->M : 1.f;
+  return sync_fwd_apply(a, work, states, nranks, rank_stride, nmul, stream);
 }
 
 static int sync_bwd_check(const pkc_dense_bwd_args* a, const float* work) {

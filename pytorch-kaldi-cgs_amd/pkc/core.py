@@ -273,9 +273,13 @@ def run_nn(data_name, data_set, data_end_index, fea_dict, lab_dict, arch_dict, c
     if to_do == "forward" and rank != 0:
         pass
     elif seq_model:
+        # SyncBN (see the frame branch below): here also the recurrent layers' gate BatchNorms
+        sbn = None
+        if ws_eff > 1 and to_do == "train" and config["exp"].get("sync_bn", "False") == "True":
+            sbn = DP.SyncBatchNorm()
         eng = Engine(nns, arch_opts, lines, fea_cols, lab_names, batch=batch_size, seed=eseed,
                      train=(to_do == "train"), max_len=int(lens.max()), grad_scale=1.0 / ws_eff,
-                     prec=prec)
+                     sync_bn=sbn, prec=prec)
         for net_name in nns:
             pt = config[arch_dict[net_name][0]]["arch_pretrain_file"]
             if pt != "none" and to_do == "train":
@@ -286,9 +290,10 @@ def run_nn(data_name, data_set, data_end_index, fea_dict, lab_dict, arch_dict, c
                        sentences=DP.shard_sentences(chunk.end_index, rank, ws_eff))
         if ws_eff > 1:
             eng.n_batches = DP.agree_min(eng.n_batches, device=eng.dev)
-            if to_do == "train":        # frame-weighted sequence DP: the chunk's loss scales
-                eng.frame_scales = DP.frame_weights(eng.sent_len, eng.B, eng.n_batches,
-                                                    device=eng.dev)
+            if to_do == "train":        # frame-weighted sequence DP: the chunk's loss scales and,
+                # for SyncBN, every batch's global row count (the same one collective)
+                eng.frame_scales, eng.global_rows = DP.frame_rows(eng.sent_len, eng.B,
+                                                                  eng.n_batches, device=eng.dev)
         post_files, priors = {}, {}
         if to_do == "forward":
             for oi, out in enumerate(forward_outs):

@@ -18,6 +18,10 @@ mean of the ranks' batch losses — each rank's loss being the reference's own p
 No other collective is on the data path.  Per chunk: the loss / err totals are summed for the
 .info file, and the BatchNorm running statistics (updated locally from each rank's batches) are
 averaged so the saved model is one replica.
+
+Optional ([exp] sync_bn = True, SyncBatchNorm below): BatchNorm statistics over the global batch,
+two small all-reduces per BatchNorm'd layer and step; every rank's running statistics are then
+identical and the chunk-end average changes nothing.
 """
 import os
 
@@ -92,15 +96,24 @@ def frame_weights(sent_len, B, n_batches, device=None):
     of the global batch i is T_r[i] / sum_r' T_r'[i] (see frame_weight).  The T's follow from the
     sentence lengths alone (the random left padding does not change them), so ONE all-reduce per
     chunk replaces the per-step scalar all-reduce and its host sync.  Returns float64 (n_batches,)."""
+    return frame_rows(sent_len, B, n_batches, device)[0]
+
+
+def frame_rows(sent_len, B, n_batches, device=None):
+    """frame_weights and, beside the scales, every batch's GLOBAL row count sum_r T_r[i] * B
+    (int64 (n_batches,)): the population of a synchronised BatchNorm under sequence DP, where the
+    ranks' padded lengths differ and world * rows would be wrong (Engine.global_rows).  The same
+    ONE all-reduce per chunk; nothing per step.  Returns (scales, totals)."""
     lens = np.asarray(sent_len, dtype=np.int64)[:n_batches * B].reshape(n_batches, B)
     T = lens.max(1).astype(np.float64)
     rank, ws = world()
     if ws == 1:
-        return np.ones(n_batches)
+        return np.ones(n_batches), lens.max(1).astype(np.int64) * int(B)
     t = torch.zeros((ws, n_batches), dtype=torch.float64, device=device)
     t[rank] = torch.from_numpy(T).to(t.device)
     dist.all_reduce(t)
-    return T / t.sum(0).cpu().numpy()
+    tot = t.sum(0).cpu().numpy()
+    return T / tot, np.rint(tot).astype(np.int64) * int(B)
 
 
 def sum_scalars(vals, device=None):
@@ -166,11 +179,22 @@ class GradAllReduce:
 
 
 class SyncBatchNorm:
-    """Engine(sync_bn=SyncBatchNorm()): the MLP layers' training-mode BatchNorm statistics over
-    the GLOBAL batch of all ranks (SURVEY 8e's optional SyncBN; its DP parity recipe: R ranks on a
-    split global batch equal one process on the whole batch).  Per BatchNorm layer and direction
-    one small all-reduce: the ranks' (n, mean, M2) column states (forward, merged in rank order by
-    pkc_dense_fwd_sync_apply) and the column sums of dy, dy * xhat (backward).  Eager steps only
+    """Engine(sync_bn=SyncBatchNorm()): the training-mode BatchNorm statistics of the MLP layers
+    and of the recurrent layers' gate projections (LSTM, GRU, liGRU, minimalGRU, RNN;
+    unidirectional and shared-weight bidirectional) over the GLOBAL batch of all ranks (SURVEY
+    8e's optional SyncBN; its DP parity recipe: R ranks on a split global batch equal one process
+    on the whole batch).
+
+    Per BatchNorm'd layer and direction ONE small all-reduce.  Forward: the ranks' (n, mean, M2)
+    column states, merged in rank order (Chan, so unequal row counts per rank are exact) by
+    pkc_dense_fwd_sync_apply — an MLP layer's [R][3N] floats; a recurrent layer's G gate
+    BatchNorms packed as [R][G][3H] and merged by pkc_dense_fwd_sync_apply_packed.  Backward: the
+    column sums of dy, dy * xhat — [2N], or [G][2H] for a recurrent layer — applied over the
+    global row count.  In a sequence engine that count is sum_r T_r * B of the step's batch
+    (Engine.global_rows from pkc.dist.frame_rows: one all-reduce per chunk, nothing per step).
+    Input-normalisation and convolution BatchNorms are not covered: the Engine refuses them.
+
+    `calls` counts the collectives issued (2 per BatchNorm'd layer and step).  Eager steps only
     (Engine.capture returns False with it)."""
 
     def __init__(self, group=None):

@@ -259,17 +259,22 @@ class Engine:
         # global batch's rows, pkc.dist.frame_weights: one collective per chunk, none per step),
         # indexed by batch; None: the fixed grad_scale
         self.frame_scales = None
-        # SyncBN (pkc.dist.SyncBatchNorm): the MLP layers' BatchNorm statistics over all ranks
+        # sequence DP with SyncBN: every batch's GLOBAL row count sum_r T_r * B of the bound chunk
+        # (pkc.dist.frame_rows, the same one collective per chunk), indexed by batch: the
+        # population of the synchronised BatchNorm backward (the ranks' padded T_r differ, so it
+        # is not rows * world); a sequence engine on more than one rank refuses to step without it
+        self.global_rows = None
+        self.step_rows = 0                     # the current step's entry of it
+        # SyncBN (pkc.dist.SyncBatchNorm): the BatchNorm statistics of the MLP layers and of the
+        # recurrent layers' gate projections over all ranks
         self.sync_bn = sync_bn
         if sync_bn is not None:
-            # SyncBN covers the BatchNorm of the MLP layers (the DP parity recipe);
-            # input-normalisation BatchNorms and the recurrent layers' gate BatchNorms keep
-            # per-rank statistics: refuse a model whose parity would silently not hold
+            if self.external:
+                raise NotImplementedError("sync_bn: not with the architecture plug-in (external)")
+            # SyncBN covers the BatchNorm of the MLP layers and of the recurrent gate projections
+            # (the DP parity recipe); input-normalisation and convolution BatchNorms
+            # keep per-rank statistics: refuse a model whose parity would silently not hold
             for a, net in nets.items():
-                if getattr(net, "seq_model", False) and any(
-                        sp.get("bn") for sp in net.layer_specs()):
-                    raise NotImplementedError("sync_bn: %s is recurrent with BatchNorm (its gate "
-                                              "statistics are per rank)" % a)
                 if any(sp.get("kind") == "bn" for sp in (net.input_norm_specs() if hasattr(net, "input_norm_specs") else [])):
                     raise NotImplementedError("sync_bn: %s has an input BatchNorm (per-rank "
                                               "statistics)" % a)
@@ -717,8 +722,11 @@ class Engine:
             # host side of the per-batch metadata upload: a ring of pinned slots, each reused only
             # after the copy that read it has run (its event), so the upload never waits on the
             # device queue (the reference's per-batch host round trip, core.py:186-214)
-            self.meta_ring = [torch.zeros(4 * self.B, dtype=torch.int64).pin_memory()
+            # (pageable on a cpu device: construction-only engines of the host tests)
+            self.meta_ring = [torch.zeros(4 * self.B, dtype=torch.int64)
                               for _ in range(SEQ_META_SLOTS)]
+            if dev.type == "cuda":
+                self.meta_ring = [m.pin_memory() for m in self.meta_ring]
             self.meta_ev = [None] * SEQ_META_SLOTS
             self.meta_k = 0
         if self.external:
@@ -876,6 +884,11 @@ class Engine:
                       dx=_f32((G * MAX_SPLITS + xres) * M * K, dev),
                       dW=[None] * G, db=[None] * G, dU=[None] * G, dgamma=[None] * G,
                       dbeta=[None] * G, dgamma_ln=[None], dbeta_ln=[None])
+            if self.sync_bn is not None and sp["bn"]:
+                # SyncBN: the ranks' (n, mean, M2) states of the G gate BatchNorms, [R][G][3H], and
+                # the gates' backward column sums, [G][2H]: one collective per layer and pass
+                lb.update(bn_states=_f32(self.sync_bn.world * G * 3 * H, dev),
+                          bn_sums=_f32(G * 2 * H, dev))
             if sp.get("ln"):
                 lb.update(ln_xhat=_f32(T * B2 * H, dev), ln_stat=_f32(2 * T * B2, dev),
                           ln_g=_f32(T * B2 * H, dev), ln_pg=_f32(2 * H, dev))
@@ -922,7 +935,8 @@ class Engine:
         optimizer epilogue applies (see pattern_effective_masks)."""
         eff = {}
         for net in self.nets.values():
-            eff.update(pattern_effective_masks(net, self._stream()))
+            if getattr(net, "if_pattern", False):     # (no stream asked for without one)
+                eff.update(pattern_effective_masks(net, self._stream()))
         for n in self.nodes:
             if n.rec:
                 for li, sp in enumerate(n.layers):
@@ -1096,7 +1110,8 @@ class Engine:
                 self.prune_list.append((n_.W, float(n_.spec["prune"])) + n_.quant_of(n_.W))
         self.prune_work = (torch.zeros(L.lib().pkc_prune_work_size(), dtype=torch.uint8,
                                        device=self.dev) if self.prune_list else None)
-        self.apply_weight_masks(self._stream())
+        if self.dev.type == "cuda":          # (a cpu device: construction only, nothing launches)
+            self.apply_weight_masks(self._stream())
 
     def apply_weight_masks(self, s):
         """The reference multiplies the masks into W in place (and QuantizeLinear clamps W to
@@ -1849,6 +1864,13 @@ class Engine:
                         "pkc_fakequant_input", ptr(prev["y"]), ptr(lb["xq"]), M * K, sp["ibits"],
                         n.G, ptr(lb["qwork"]), s)
             xin, _ = self._rec_inputs(n, li)
+            # SyncBN: every gate's statistics pass first (z staged in the gate's xhat, its state
+            # into this rank's row of the layer's [R][G][3H] buffer), ONE collective, then every
+            # gate's merge + apply
+            sync = train and sp["bn"] and lb.get("bn_states") is not None
+            sync_args = []
+            if sync:
+                lb["bn_states"].zero_()
             for g in range(n.G):
                 x_ptr, ldx = xin[g]
                 kt = self._wt(sp["W"][g], False)
@@ -1880,8 +1902,24 @@ class Engine:
                     xhat=lb["xhat"].data_ptr() + 4 * g * M * H,
                     out=lb["wpre"].data_ptr() + 4 * g * M * H,
                     count_n=M * (2 if sp["bidir"] else 1))
+                if sync:
+                    row = (self.sync_bn.rank * n.G + g) * 3 * H
+                    self._k("rnn_bn_fwd_stats H=%d" % H, 0, 4.0 * M * H * (sf + 1),
+                            "pkc_dense_fwd_stats", C.byref(a), ptr(lb["work"]),
+                            C.c_void_p(lb["bn_states"].data_ptr() + 4 * row), s)
+                    sync_args.append(a)
+                    continue
                 self._k("rnn_bn_fwd H=%d" % H, 0, 4.0 * M * H * (sf + 2), "pkc_dense_fwd",
                         C.byref(a), ptr(lb["work"]), s)
+            if sync:
+                # count_n (this rank's rows as BatchNorm1d sees them: 2 M when bidirectional)
+                # scales the merged global count for the unbiased running_var the same way
+                self.sync_bn(lb["bn_states"])
+                for g, a in enumerate(sync_args):
+                    self._k("rnn_bn_fwd_sync_apply H=%d" % H, 0, 4.0 * M * H * 3,
+                            "pkc_dense_fwd_sync_apply_packed", C.byref(a), ptr(lb["work"]),
+                            C.c_void_p(lb["bn_states"].data_ptr() + 4 * g * 3 * H),
+                            self.sync_bn.world, n.G * 3 * H, s)
             ra = self._rnn_args(n, li, train, T)
             if ra.step_bf16 or ra.qh_exact:   # this step's U (after the last update) as bf16
                 for g in range(n.G):
@@ -2158,7 +2196,7 @@ class Engine:
             self.sync_bn(n.bn_sums)
             self._k("dense_bwd_sync_apply N=%d" % n.N, 0, 4.0 * M * n.N * 3,
                     "pkc_dense_bwd_sync_apply", C.byref(a), ptr(n.work), ptr(n.bn_sums),
-                    M * self.sync_bn.world, s)
+                    self._sync_rows(), s)
         elif n.bnb_now:                      # statistics came with the consumer's dX matmul
             self._k("dense_bwd_pre N=%d" % n.N, 0, 4.0 * M * n.N * 3, "pkc_dense_bwd_pre",
                     C.byref(a), ptr(n.work), 128, s)
@@ -2169,6 +2207,15 @@ class Engine:
             # the Linear's bias sits in front of the LayerNorm (per-row statistics): its gradient
             # is the column sum of the LayerNorm's input gradient
             self._ln_bwd(n, s, ptr(n.dz_ln), 1, 0, n.dz, n.db)
+
+    def _sync_rows(self):
+        """Rows of the global batch a synchronised BatchNorm backward runs over.  Frame batches:
+        every rank has M rows.  Sequence batches: the ranks' padded T_r differ, so the count is
+        the step's entry of global_rows (sum_r T_r * B, set in train_step from the chunk's
+        bind-time all-reduce: no collective or host sync here)."""
+        if self.seq and self.sync_bn.world > 1:
+            return self.step_rows
+        return self.M * self.sync_bn.world
 
     def _norm_dx(self, n):
         """Where an input normalisation writes its input gradient: its slab of the producer's
@@ -2302,6 +2349,8 @@ class Engine:
             wbf = (bool(ra.step_bf16) and lb.get("dz_h") is not None and ldx == K
                    and n.cand is None)
             dzs = []
+            sync = sp["bn"] and lb.get("bn_sums") is not None     # SyncBN, as in _rec_fwd
+            sync_args = []
             for g in range(n.G):
                 bn = sp["bnm"][g]
                 a = L.DenseBwdArgs(M=M, N=H, nslab=1, gslab=lb["dpre"].data_ptr() + 4 * g * M * H,
@@ -2315,9 +2364,24 @@ class Engine:
                                    dbeta=lb["dbeta"][g].data_ptr() if sp["bn"] else None,
                                    dbias=lb["db"][g].data_ptr() if lb["db"][g] is not None else None,
                                    dz_bf16=lb["dz_h"].data_ptr() + 2 * g * M * H if wbf else None)
+                dzs.append(lb["dz"].data_ptr() + 4 * g * M * H)
+                if sync:
+                    self._k("rnn_bn_bwd_stats H=%d" % H, 0, 4.0 * M * H * 3, "pkc_dense_bwd_stats",
+                            C.byref(a), ptr(lb["work"]),
+                            C.c_void_p(lb["bn_sums"].data_ptr() + 4 * g * 2 * H), s)
+                    sync_args.append(a)
+                    continue
                 self._k("rnn_bn_bwd H=%d" % H, 0, 4.0 * M * H * 4, "pkc_dense_bwd", C.byref(a),
                         ptr(lb["work"]), s)
-                dzs.append(lb["dz"].data_ptr() + 4 * g * M * H)
+            if sync:
+                # the gates' column sums in ONE collective; dgamma / dbeta / dbias stay this
+                # rank's sums (the gradient all-reduce completes them)
+                self.sync_bn(lb["bn_sums"])
+                for g, a in enumerate(sync_args):
+                    self._k("rnn_bn_bwd_sync_apply H=%d" % H, 0, 4.0 * M * H * 3,
+                            "pkc_dense_bwd_sync_apply", C.byref(a), ptr(lb["work"]),
+                            C.c_void_p(lb["bn_sums"].data_ptr() + 4 * g * 2 * H),
+                            self._sync_rows(), s)
             h16 = None
             if wbf:
                 self._k("rnn_cast_x_bf16 %dx%d" % (M, K), 0, 6.0 * M * K, "pkc_cast_bf16",
@@ -2676,6 +2740,11 @@ class Engine:
                 # share of all ranks' rows, so the summed gradient is that of the mean over every
                 # row of the global batch, not the mean of unequal batch means
                 self.grad_scale = float(self.frame_scales[getattr(batch, "index", self.batch_i)])
+            if self.sync_bn is not None and self.sync_bn.world > 1:
+                if self.global_rows is None:
+                    raise ValueError("sync_bn on %d ranks: a sequence engine needs global_rows "
+                                     "(pkc.dist.frame_rows)" % self.sync_bn.world)
+                self.step_rows = int(self.global_rows[getattr(batch, "index", self.batch_i)])
             self._upload_seq_meta(batch)
             if (self.seq_graphs is not None and allreduce is None and self.frame_scales is None
                     and self._seq_seen(batch)):

@@ -68,11 +68,12 @@ def rec_opts(cfg_name):
     return "LSTM", d, (16 if cfg_name == "c4" else 12)
 
 
-def build(cfg_name, seed=2234, rank=0, world=1, prec="fp32"):
+def build(cfg_name, seed=2234, rank=0, world=1, prec="fp32", sync_bn=None):
     """Engine + nets of `cfg_name` bound to a synthetic length-sorted chunk of 64 * B sentences.
     Data parallelism (world > 1): every rank builds the same model from the same seeds and draws
     its OWN chunk (weak scaling: B sentences per rank and step), its loss scaled per batch by its
-    share of the global batch's padded rows (pkc.dist.frame_weights, one collective per chunk)."""
+    share of the global batch's padded rows (pkc.dist.frame_weights, one collective per chunk).
+    sync_bn: a pkc.dist.SyncBatchNorm (the gate BatchNorms over the global batch)."""
     import pkc.neural_networks as NN
     from pkc import _lib as L
     from pkc.engine import Engine, parse_model
@@ -117,12 +118,13 @@ def build(cfg_name, seed=2234, rank=0, world=1, prec="fp32"):
         max_len = -DP.agree_min(-max_len, device="cuda")
     eng = Engine(nets, opts, parse_model(model), {"fea": (0, 440)}, ["lab_cd", "lab_mono"],
                  batch=B, max_len=max_len, seed=seed + rank, grad_scale=1.0 / world,
-                 prec=L.PREC_BF16 if prec == "bf16" else L.PREC_FP32)
+                 sync_bn=sync_bn, prec=L.PREC_BF16 if prec == "bf16" else L.PREC_FP32)
     eng.bind_chunk(feats, labs, N, end_index=end)
     if world > 1:
         from pkc import dist as DP
         eng.n_batches = DP.agree_min(eng.n_batches, device="cuda")
-        eng.frame_scales = DP.frame_weights(eng.sent_len, eng.B, eng.n_batches, device="cuda")
+        eng.frame_scales, eng.global_rows = DP.frame_rows(eng.sent_len, eng.B, eng.n_batches,
+                                                          device="cuda")
     return eng, nets, B
 
 
@@ -146,14 +148,14 @@ def alg_flops_per_row(nets):
 
 
 def run(cfg_name, steps, warmup, allreduce=None, rank=0, world=1, prec="fp32", graphs=False,
-        hold=None):
+        hold=None, sync_bn=None):
     """Times `steps` sentence batches after `warmup` (barrier + synchronize on both sides of the
     timed region; the max over ranks).  frames_per_s is the whole job's: every rank's real frames
     over that time.  graphs: the steps replay per-T captured graphs (Engine.capture), captured in
     an untimed pass over the timed batches first (steady state: every T seen before); the
     capture pass's rate is reported beside it.  hold: a dict that receives the engine and the
     nets as they stand after the last timed step ("eng", "nets")."""
-    eng, nets, B = build(cfg_name, rank=rank, world=world, prec=prec)
+    eng, nets, B = build(cfg_name, rank=rank, world=world, prec=prec, sync_bn=sync_bn)
     if hold is not None:
         hold.update(eng=eng, nets=nets)
     cap_s = None
