@@ -12,6 +12,13 @@ difference stays at fp32 rounding.
                                          h = z h + (1 - z) hc
   LSTM   neural_networks.py:1087-1092   f, i, o = sig(w. + U. h); c = i act(wc + Uc h) m + f c;
                                          h = o act(c)
+  GRU    neural_networks.py:1390-1396   z, r = sig(w. + U. h); hc = act(wh + Uh (r h)) * m;
+                                         h = z h + (1 - z) hc
+  minimalGRU :1751-1755                  GRU with r replaced by z (Uh reads z h)
+  RNN    :1905-1907                      h = act(wh + Uh h) * m
+  LayerNorm of h (use_laynorm, :40-51 applied after every cell update): ln_h_fwd / ln_h_bwd; the
+  backward functions take `ln` = the saved (gamma, xhat, den, std) and pass dL/dh_t (post-norm)
+  through ln_h_bwd before the gate gradients; the carries then act on the pre-norm gradient.
 The backward functions are the chain rule of those expressions (what autograd computes for the
 reference's loop): the BPTT of step t from dL/dy_t, the products of step t+1's gate gradients with
 U (dh_t = sum_g dgates_g,t+1 U_g) and the carried dL/dh (liGRU: g_{t+1} z_{t+1}) / dL/dc (LSTM:
@@ -92,39 +99,80 @@ def steps_lstm_fwd(hA, hprev, cprev, U, wpre, mask, act):
     return f, i, o, cc, c, o * act_fwd(act, c)
 
 
-def steps_ligru_bwd(dh_y, dgA, U, z, hcr, hprev, mask, act):
+def ln_h_fwd(h_cell, gamma, beta, eps):
+    """LayerNorm of the new hidden state (neural_networks.py:40-51): h = gamma (h_cell - mean) /
+    (std + eps) + beta over the last dimension, std unbiased.  Returns (xhat, den = std + eps, std,
+    h); den and std keep a last dimension of 1."""
+    mu = h_cell.mean(-1, keepdim=True)
+    sd = h_cell.std(-1, keepdim=True)
+    den = sd + eps
+    xhat = (h_cell - mu) / den
+    return xhat, den, sd, gamma * xhat + beta
+
+
+def ln_h_bwd(g_post, gamma, xhat, den, std):
+    """Backward of ln_h_fwd from its saved xhat / den / std: with gh = g_post gamma,
+    dh_cell = (gh - mean gh) / den - xhat sum(gh xhat) / ((H - 1) std); the second term is 0 where
+    std = 0 (torch's std backward masks that case).  Returns (dh_cell, dgamma, dbeta), the
+    parameter gradients summed over every leading dimension."""
+    H = g_post.shape[-1]
+    gh = g_post * gamma
+    sgx = (gh * xhat).sum(-1, keepdim=True)
+    safe = torch.where(std > 0, std, torch.ones_like(std))
+    kk = torch.where(std > 0, sgx / ((H - 1) * safe), torch.zeros_like(sgx))
+    dh = (gh - gh.mean(-1, keepdim=True)) / den - xhat * kk
+    return dh, (g_post * xhat).reshape(-1, H).sum(0), g_post.reshape(-1, H).sum(0)
+
+
+def _pre_norm(ln, t, g_post):
+    """dL/dh_t before the LayerNorm of h (ln = None: no norm).  ln = dict(gamma, xhat, den, std
+    [, g_post]): with g_post (T, R, H) given (a run's saved post-norm gradients) step t is
+    restated from it, so nothing compounds through the norm's backward."""
+    if ln is None:
+        return g_post
+    gp = ln["g_post"][t] if ln.get("g_post") is not None else g_post
+    return ln_h_bwd(gp, ln["gamma"], ln["xhat"][t], ln["den"][t], ln["std"][t])[0]
+
+
+def steps_ligru_bwd(dh_y, dgA, U, z, hcr, hprev, mask, act, ln=None):
     """BPTT of the liGRU steps: dh_y (T, R, H) dL/dh_t from the layer output, dgA [dz, da] (T, R,
     H) the gate gradients of every step as the BPTT products read them (fp32, or their bf16
     copies), U = [Uz, Uh], z / hcr / hprev the forward's saved tensors.  The recurrent part of
     dL/dh_t is dgA_t+1 @ U (from the run's operands) + g_{t+1} z_{t+1} (this function's own
-    carry).  Returns the gate gradients (dz_pre, da_pre) (T, R, H) and the g chain."""
+    carry).  Returns the gate gradients (dz_pre, da_pre) (T, R, H) and the g chain; with ln (see
+    _pre_norm) g is the pre-norm gradient and the post-norm gradients are returned as a fourth
+    value."""
     T = dh_y.shape[0]
     prod = torch.zeros_like(dh_y)
     prod[:-1] = dgA[0][1:] @ U[0] + dgA[1][1:] @ U[1]   # dh_t from step t + 1's products
     dz = torch.empty_like(dh_y)
     da = torch.empty_like(dh_y)
     gs = torch.empty_like(dh_y)
+    gp = torch.empty_like(dh_y)
     g = None
     for t in range(T - 1, -1, -1):
-        gt = dh_y[t] + prod[t] + (g * z[t + 1] if g is not None else 0)
+        gp[t] = dh_y[t] + prod[t] + (g * z[t + 1] if g is not None else 0)
+        gt = _pre_norm(ln, t, gp[t])
         hc = hcr[t] * mask
         dz[t] = gt * (hprev[t] - hc) * z[t] * (1 - z[t])
         da[t] = gt * (1 - z[t]) * mask * act_bwd_out(act, hcr[t])
         gs[t] = g = gt
-    return dz, da, gs
+    return (dz, da, gs) if ln is None else (dz, da, gs, gp)
 
 
-def steps_lstm_bwd(dh_y, dgA, U, f, i, o, cc, c, cprev, mask, act):
+def steps_lstm_bwd(dh_y, dgA, U, f, i, o, cc, c, cprev, mask, act, ln=None):
     """BPTT of the LSTM steps (gate order f, i, o, cand): the recurrent part of dL/dh_t is
     sum_g dgA_g,t+1 @ U_g; dL/dc_t = g o act'(act(c_t)) + dc_{t+1} f_{t+1} (own carry).  Returns
-    the four pre-activation gradients (T, R, H)."""
+    the four pre-activation gradients (T, R, H); with ln (see _pre_norm) also the post-norm
+    gradients, as a fifth element."""
     T = dh_y.shape[0]
     prod = torch.zeros_like(dh_y)
     prod[:-1] = sum(dgA[q][1:] @ U[q] for q in range(4))
     out = [torch.empty_like(dh_y) for _ in range(4)]
+    gp = dh_y + prod
     carry = None
     for t in range(T - 1, -1, -1):
-        g = dh_y[t] + prod[t]
+        g = _pre_norm(ln, t, gp[t])
         tc = act_fwd(act, c[t])
         dc = g * o[t] * act_bwd_out(act, tc) + (carry if carry is not None else 0)
         out[0][t] = dc * cprev[t] * f[t] * (1 - f[t])
@@ -132,7 +180,83 @@ def steps_lstm_bwd(dh_y, dgA, U, f, i, o, cc, c, cprev, mask, act):
         out[2][t] = g * tc * o[t] * (1 - o[t])
         out[3][t] = dc * i[t] * mask * act_bwd_out(act, cc[t])
         carry = dc * f[t]
-    return out
+    return out if ln is None else out + [gp]
+
+
+def steps_gru_fwd(hA, hprev, U, wpre, mask, act, rhA=None):
+    """GRU (neural_networks.py:1390-1396), gates (z, r, h): U = [Uz, Ur, Uh], wpre likewise.  hA
+    the operand of the Uz / Ur products, rhA the operand of the Uh product (a run's saved r h;
+    None: this function's own).  Returns (z, r, r h, act(a), h)."""
+    z = torch.sigmoid(wpre[0] + hA @ U[0].t())
+    r = torch.sigmoid(wpre[1] + hA @ U[1].t())
+    rh = r * hprev
+    hcr = act_fwd(act, wpre[2] + (rh if rhA is None else rhA) @ U[2].t())
+    return z, r, rh, hcr, z * hprev + (1 - z) * (hcr * mask)
+
+
+def steps_mingru_fwd(hA, hprev, U, wpre, mask, act, zhA=None):
+    """minimalGRU (:1751-1755), gates (z, h): U = [Uz, Uh]; zhA the operand of the Uh product (a
+    run's saved z h; None: own).  Returns (z, z h, act(a), h)."""
+    z = torch.sigmoid(wpre[0] + hA @ U[0].t())
+    zh = z * hprev
+    hcr = act_fwd(act, wpre[1] + (zh if zhA is None else zhA) @ U[1].t())
+    return z, zh, hcr, z * hprev + (1 - z) * (hcr * mask)
+
+
+def steps_rnn_fwd(hA, hprev, U, wpre, mask, act):
+    """RNN (:1905-1907): U = [Uh], wpre = [wh].  Returns (act(a), h)."""
+    hcr = act_fwd(act, wpre[0] + hA @ U[0].t())
+    return hcr, hcr * mask
+
+
+def steps_gru_bwd(dh_y, dgA, U, z, r, hcr, hprev, mask, act, ln=None):
+    """BPTT of the GRU steps, dgA = [dz, dr, da] as the products read them:
+    g_t = dy_t + dz_{t+1} Uz + dr_{t+1} Ur + g_{t+1} z_{t+1} + d(rh)_{t+1} r_{t+1}, with
+    d(rh)_t = da_t Uh (a product of the run's da_t), dz = g (h - hc) z (1 - z),
+    da = g (1 - z) m act'(hcr), dr = d(rh) h r (1 - r).  Returns ([dz, dr, da], the post-norm
+    gradients g before ln (= g without it))."""
+    T = dh_y.shape[0]
+    drh = dgA[2] @ U[2]
+    prod = torch.zeros_like(dh_y)
+    prod[:-1] = dgA[0][1:] @ U[0] + dgA[1][1:] @ U[1] + drh[1:] * r[1:]
+    dz, da, gp = torch.empty_like(dh_y), torch.empty_like(dh_y), torch.empty_like(dh_y)
+    g = None
+    for t in range(T - 1, -1, -1):
+        gp[t] = dh_y[t] + prod[t] + (g * z[t + 1] if g is not None else 0)
+        g = _pre_norm(ln, t, gp[t])
+        dz[t] = g * (hprev[t] - hcr[t] * mask) * z[t] * (1 - z[t])
+        da[t] = g * (1 - z[t]) * mask * act_bwd_out(act, hcr[t])
+    return [dz, drh * hprev * r * (1 - r), da], gp
+
+
+def steps_mingru_bwd(dh_y, dgA, U, z, hcr, hprev, mask, act, ln=None):
+    """BPTT of the minimalGRU steps, dgA = [dz, da]: g_t = dy_t + dz_{t+1} Uz +
+    (g_{t+1} + d(zh)_{t+1}) z_{t+1}, d(zh)_t = da_t Uh, da = g (1 - z) m act'(hcr),
+    dz = (g (h - hc) + d(zh) h) z (1 - z).  Returns ([dz, da], post-norm gradients)."""
+    T = dh_y.shape[0]
+    dzh = dgA[1] @ U[1]
+    prod = torch.zeros_like(dh_y)
+    prod[:-1] = dgA[0][1:] @ U[0] + dzh[1:] * z[1:]
+    dz, da, gp = torch.empty_like(dh_y), torch.empty_like(dh_y), torch.empty_like(dh_y)
+    g = None
+    for t in range(T - 1, -1, -1):
+        gp[t] = dh_y[t] + prod[t] + (g * z[t + 1] if g is not None else 0)
+        g = _pre_norm(ln, t, gp[t])
+        dz[t] = (g * (hprev[t] - hcr[t] * mask) + dzh[t] * hprev[t]) * z[t] * (1 - z[t])
+        da[t] = g * (1 - z[t]) * mask * act_bwd_out(act, hcr[t])
+    return [dz, da], gp
+
+
+def steps_rnn_bwd(dh_y, dgA, U, hcr, mask, act, ln=None):
+    """BPTT of the RNN steps, dgA = [da]: g_t = dy_t + da_{t+1} Uh, da = g m act'(hcr).  Returns
+    ([da], post-norm gradients)."""
+    T = dh_y.shape[0]
+    gp = dh_y.clone()
+    gp[:-1] += dgA[0][1:] @ U[0]
+    da = torch.empty_like(dh_y)
+    for t in range(T - 1, -1, -1):
+        da[t] = _pre_norm(ln, t, gp[t]) * mask * act_bwd_out(act, hcr[t])
+    return [da], gp
 
 
 def pre_grad_input_time(dg, B, bidir):
