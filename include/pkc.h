@@ -27,7 +27,8 @@ extern "C" {
  * 8: pkc_rnn_args.qh_exact (exact quantised-h step products).
  * pkc_combine_args and its three entry points joined under 9 without a bump: no existing struct or
  * entry point changed (tests/test_model_ops_cpu.py checks the new struct's layout).  pkc_rnn_std_args
- * and pkc_rnn_std_fwd / _bwd joined the same way (tests/test_cudnn_cpu.py checks its layout). */
+ * and pkc_rnn_std_fwd / _bwd joined the same way (tests/test_cudnn_cpu.py checks its layout), and so
+ * did pkc_sru_args with pkc_sru_fwd / _bwd / _mask_x / _dx (tests/test_sru_cpu.py). */
 #define PKC_ABI_VERSION 9
 
 enum { PKC_OK = 0, PKC_ERR_ARG = -1, PKC_ERR_HIP = -2, PKC_ERR_IO = -3, PKC_ERR_UNSUPPORTED = -4 };
@@ -669,6 +670,64 @@ typedef struct {
 } pkc_rnn_std_args;
 int pkc_rnn_std_fwd(const pkc_rnn_std_args* a, void* stream);
 int pkc_rnn_std_bwd(const pkc_rnn_std_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Simple Recurrent Unit (Lei et al., EMNLP 2018, the v2 cell with the highway scaling alpha): the
+ * time loop of one layer, both directions, as ONE launch.  A pkc extension: the reference keeps its
+ * SRU class commented out, so nothing here is pinned against it.  Additive to ABI 9: a new
+ * struct and new entry points only.  n_out = ndir * d; column j belongs to direction j / d, and
+ * direction 1 walks t = T-1 .. 0.  k = 4 when the skip term is on and n_in != n_out, else 3.
+ *   u        (T, B, n_out*k), rows in natural time: the projection X weight, gate g of column j at
+ *            j*k + g (k = 4: 16-byte aligned, one 16-byte load per thread);
+ *   x, ldx   k = 3 with the skip term: the layer's (undropped) input rows, (T*B) rows of ldx >= n_out
+ *            floats whose first n_in = n_out columns are read; else unused;
+ *   weight_c (2 n_out) = [v_f | v_r], bias (2 n_out) = [b_f | b_r].
+ * Forward (c_{-1} = 0; pads are ordinary rows):
+ *   f = sig(u1 + v_f c_{t-1} + b_f), r = sig(u2 + v_r c_{t-1} + b_r), c = f c_{t-1} + (1 - f) u0,
+ *   x' = u3 (k = 4) | alpha x (k = 3, skip != 0) | 0 (skip == 0),
+ *   h = r g(c) m_c + (1 - r) x',   g = act: PKC_ACT_LINEAR, PKC_ACT_RELU or PKC_ACT_TANH.
+ * Saves cs (T, B, n_out) = c and writes y (T, B, n_out) = h.  m_c[b, j] = keep / (1 - drop_p) in
+ * training with drop_p > 0, else 1: ONE mask for all t, keep ~ Bernoulli(1 - drop_p) drawn from the
+ * counter-hash stream of pkc_dense_fwd (index b * n_out + j) or read from keep_in; keep (u8,
+ * (B, n_out)) is written for the backward.
+ * Backward (pkc_sru_bwd; carry dc from 0, dh = the sum of the dy_nslab slabs of dy):
+ *   dr = dh (g(c) m_c - x'), dx' = dh (1 - r), dc += dh r m_c g'(c),
+ *   du0 = dc (1 - f), du1 = da_f = dc (c_{t-1} - u0) f (1 - f), du2 = da_r = dr r (1 - r),
+ *   du3 = dx' (k = 4); k = 3 with skip: dxh[t, b, j] = alpha dx';  dc <- dc f + da_f v_f + da_r v_r.
+ * Writes du (the layout of u), dxh (T, B, n_out), dwc = [sum da_f c_{t-1} | sum da_r c_{t-1}] and
+ * dbias = [sum da_f | sum da_r]: summed over T in registers, the per-sentence sums stored in work
+ * ((B, 4, n_out) floats) and added over b in fixed order by a second small kernel.  The gates are
+ * recomputed from u and cs.  The caller then takes d weight = X^T dU and dX = dU weight^T (+ dxh) as
+ * plain matmuls.  No atomics: reruns are bit-identical and a bidirectional call equals two
+ * one-direction calls bit for bit.  n_in is only checked: k = 3 with skip needs n_in == n_out, k = 4
+ * needs skip and n_in != n_out.  PKC_ERR_ARG with a pkc_last_error() text for a null pointer or a bad
+ * shape.
+ * pkc_sru_mask_x: the recurrent ("rnn") dropout of the projection's input, xt[t, b, i] =
+ * x[t, b, i] m_x[b, i] with m_x = keep / (1 - drop_p), ONE (B, n_in) mask for all t from the same
+ * stream (index b * n_in + i) or keep_in; xt is (T*B, n_in) contiguous, keep (u8) is written.
+ * pkc_sru_dx: dx = m_x * (slab_0 + .. + slab_{nslab-1}) + dxh as ONE (T*B, n_in) slab; keep == NULL:
+ * no mask, dxh == NULL: no highway gradient.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  int T, B, d, ndir, k, act, train, skip;
+  int n_in; float alpha;
+  const float* u;
+  const float* x; int64_t ldx;
+  const float* weight_c; const float* bias;
+  float* cs; float* y;
+  float drop_p; uint64_t seed; const int64_t* step_ctr; int64_t stream_id;
+  const uint8_t* keep_in;      /* optional injected keep mask (B, n_out) */
+  uint8_t* keep;               /* (B, n_out) mask in use */
+  const float* dy; int dy_nslab; int64_t dy_slab_stride;
+  float* du; float* dxh; float* dwc; float* dbias; float* work;
+} pkc_sru_args;
+int pkc_sru_fwd(const pkc_sru_args* a, void* stream);
+int pkc_sru_bwd(const pkc_sru_args* a, void* stream);
+int pkc_sru_mask_x(int T, int B, int n_in, const float* x, int64_t ldx, float drop_p, uint64_t seed,
+                   const int64_t* step_ctr, int64_t stream_id, const uint8_t* keep_in, uint8_t* keep,
+                   float* xt, void* stream);
+int pkc_sru_dx(int T, int B, int n_in, const float* slabs, int nslab, int64_t slab_stride,
+               const uint8_t* keep, float drop_p, const float* dxh, float* dx, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Host-side Kaldi ark I/O (data_io.py:770-806 write_mat; 645-711 read_mat_ark binary FM/DM).

@@ -167,7 +167,24 @@ class RnnStdArgs(C.Structure):
                 ("dgates", vp), ("ut", vp), ("work", vp)]
 
 
+# include/pkc.h pkc_sru_args: the one-launch time loop of an SRU layer
+class SruArgs(C.Structure):
+    _fields_ = [("T", C.c_int), ("B", C.c_int), ("d", C.c_int), ("ndir", C.c_int), ("k", C.c_int),
+                ("act", C.c_int), ("train", C.c_int), ("skip", C.c_int), ("n_in", C.c_int),
+                ("alpha", C.c_float), ("u", vp), ("x", vp), ("ldx", i64), ("weight_c", vp),
+                ("bias", vp), ("cs", vp), ("y", vp),
+                ("drop_p", C.c_float), ("seed", C.c_uint64), ("step_ctr", vp), ("stream_id", i64),
+                ("keep_in", vp), ("keep", vp),
+                ("dy", vp), ("dy_nslab", C.c_int), ("dy_slab_stride", i64),
+                ("du", vp), ("dxh", vp), ("dwc", vp), ("dbias", vp), ("work", vp)]
+
+
 _SIGS = {
+    "pkc_sru_fwd": (C.c_int, [C.POINTER(SruArgs), vp]),
+    "pkc_sru_bwd": (C.c_int, [C.POINTER(SruArgs), vp]),
+    "pkc_sru_mask_x": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, i64, C.c_float, C.c_uint64, vp, i64,
+                                 vp, vp, vp, vp]),
+    "pkc_sru_dx": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, C.c_int, i64, vp, C.c_float, vp, vp, vp]),
     "pkc_rnn_std_fwd": (C.c_int, [C.POINTER(RnnStdArgs), vp]),
     "pkc_rnn_std_bwd": (C.c_int, [C.POINTER(RnnStdArgs), vp]),
     "pkc_combine_ok": (C.c_int, [C.POINTER(CombineArgs), C.c_int]),

@@ -36,7 +36,8 @@ from . import _lib as L
 from ._lib import call, ptr
 # the graph vocabulary lives in pkc.graph; re-exported here, where its users import it from
 from .graph import (TENSOR_OPS, CombineNode, ConvNode, Layer, MseTerm, Node, NormLayer,  # noqa: F401
-                    RecNode, RegTerm, SeqBatch, StdRecNode, _b, _f32, conv_args, conv_post_args,
+                    RecNode, RegTerm, SeqBatch, SruNode, StdRecNode, _b, _f32, conv_args,
+                    conv_post_args,
                     parse_model, pattern_effective_masks, resolve_concat, sinc_args, sinc_bind)
 
 # split-K slab budget of a layer output (<= 8: the small-batch dense kernels sum them in
@@ -350,7 +351,8 @@ class Engine:
                 # (src may be a feed-forward node over the T*B rows, e.g. the MLP_layers_first ->
                 # liGRU of TIMIT_mfcc_fbank_fmllr_liGRU_best.cfg: its gradient is the recurrent
                 # layer 0's dX slabs, handed over in _rec_bwd)
-                node = (StdRecNode if hasattr(net, "std_cell") else RecNode)(a, net, K)
+                node = (StdRecNode if hasattr(net, "std_cell") else
+                        SruNode if hasattr(net, "sru") else RecNode)(a, net, K)
                 node.src = src
                 if src[0] == "node":
                     if src[1].rec_consumer is not None:
@@ -436,11 +438,12 @@ class Engine:
                     scal[out] = {}
                     continue
                 if op == "cost_gl":
-                    std = [arch for arch, net in self.nets.items() if hasattr(net, "std_cell")
+                    std = [arch for arch, net in self.nets.items()
+                           if (hasattr(net, "std_cell") or hasattr(net, "sru"))
                            and not getattr(net, "skip_regularization", False)]
                     if std:
                         raise NotImplementedError("cost_gl over the %s architecture %s (packed "
-                                                  "per-direction weights) is not on the pkc path"
+                                                  "gate weights) is not on the pkc path"
                                                   % (type(self.nets[std[0]]).__name__, std[0]))
                     if any(q.dim() > 2 for q in params) or any(
                             hasattr(net, "conv_specs") for net in self.nets.values()
@@ -856,9 +859,39 @@ class Engine:
         n.dysum = _f32(M * max(lb["D"] for lb in n.lbuf), dev) if REC_DY_PRESUM else None
         n.out = n.lbuf[-1]["y"]
 
+    def _alloc_sru(self, n):
+        """Buffers of an SruNode (layouts: include/pkc.h, pkc_sru_args)."""
+        M, dev, B = self.Mmax, self.dev, self.B
+        n.lbuf = []
+        K = n.K
+        n.dx_res = len(n.src[1].mse_grad) if n.src[0] == "node" else 0
+        u8 = lambda cnt: torch.zeros(cnt, dtype=torch.uint8, device=dev)      # noqa: E731
+        for sp in n.layers:
+            D, k = sp["ndir"] * sp["H"], sp["k"]
+            xres = 0 if n.lbuf else n.dx_res
+            hw = k == 3 and sp["skip"]                  # highway term alpha * x (n_in == n_out)
+            one = hw or sp["rnn_drop"] > 0              # pkc_sru_dx folds the dX slabs into one
+            lb = dict(K=K, H=sp["H"], D=D, k=k, hw=hw, one=one,
+                      u=_f32(M * D * k, dev), cs=_f32(M * D, dev), y=_f32(M * D, dev),
+                      keep=u8(B * D) if sp["drop"] > 0 else None,
+                      keep_x=u8(B * K) if sp["rnn_drop"] > 0 else None,
+                      xt=_f32(M * K, dev) if sp["rnn_drop"] > 0 else None,
+                      du=_f32(M * D * k, dev), dxh=_f32(M * D, dev) if hw else None,
+                      rwork=_f32(B * 4 * D, dev),
+                      dxs=_f32(MAX_SPLITS * M * K, dev) if one else None,
+                      dx=_f32(((1 if one else MAX_SPLITS) + xres) * M * K, dev),
+                      dweight=[None], dwc=[None], dbias=[None])
+            n.lbuf.append(lb)
+            K = D
+        n.rslab = None
+        n.dysum = _f32(M * max(lb["D"] for lb in n.lbuf), dev) if REC_DY_PRESUM else None
+        n.out = n.lbuf[-1]["y"]
+
     def _alloc_rec(self, n):
         if n.std:
             return self._alloc_std(n)
+        if n.sru:
+            return self._alloc_sru(n)
         M, dev, B, T = self.Mmax, self.dev, self.B, self.max_len
         G = n.G
         n.lbuf = []
@@ -1683,6 +1716,10 @@ class Engine:
                 for li in range(len(n.layers)):
                     out["%s.%d" % (n.arch, li)] = "fp32 steps"
                 continue
+            if n.sru:                         # SRU: the whole time loop of a layer is one launch
+                for li in range(len(n.layers)):
+                    out["%s.%d" % (n.arch, li)] = "one-launch scan"
+                continue
             for li in range(len(n.layers)):
                 a = self._rnn_args(n, li, True, self.max_len)
                 lb = n.lbuf[li]
@@ -1851,9 +1888,113 @@ class Engine:
             elif li == 0 and self.want_dx:
                 self._rec_slab_sum_ptr(lb["dx"].data_ptr(), nx, M * K, M * K, self.ext_dx, s)
 
+    def _sru_args(self, n, li, train, T):
+        sp, lb = n.layers[li], n.lbuf[li]
+        a = L.SruArgs()
+        a.T, a.B, a.d, a.ndir, a.k = T, self.B, sp["H"], sp["ndir"], sp["k"]
+        a.act, a.train, a.skip = L.ACT[sp["act"]], int(train), int(sp["skip"])
+        a.n_in, a.alpha = lb["K"], sp["alpha"]
+        a.u = lb["u"].data_ptr()
+        if lb["hw"]:
+            a.x, a.ldx = self._std_input(n, li)
+        a.weight_c, a.bias = sp["weight_c"].data_ptr(), sp["bias"].data_ptr()
+        a.cs, a.y = lb["cs"].data_ptr(), lb["y"].data_ptr()
+        a.drop_p = float(sp["drop"])
+        a.seed = self.seed
+        a.step_ctr = self.ctr.data_ptr()
+        a.stream_id = zlib.crc32(("%s.%d" % (n.arch, li)).encode())
+        din = self.rnn_drop_in.get((n.arch, li))
+        a.keep_in = din.data_ptr() if din is not None else None
+        a.keep = lb["keep"].data_ptr() if lb["keep"] is not None else None
+        a.du, a.work = lb["du"].data_ptr(), lb["rwork"].data_ptr()
+        a.dxh = lb["dxh"].data_ptr() if lb["dxh"] is not None else None
+        return a
+
+    def _sru_input(self, n, li, train):
+        """(pointer, ld) of the rows the projection of layer li multiplies: the layer's input, or
+        its rnn-dropped copy in training."""
+        if train and n.layers[li]["rnn_drop"] > 0:
+            return n.lbuf[li]["xt"].data_ptr(), n.lbuf[li]["K"]
+        return self._std_input(n, li)
+
+    def _sru_fwd(self, n, s, train):
+        """Forward of an SruNode: per layer the rnn-dropout of the input (training, p > 0), ONE
+        projection matmul U = X weight for all gates of both directions, then the one-launch time
+        loop.  The recurrence is fp32 in every pkc_prec mode; the matmul takes the mode."""
+        M, T, B = self.M, self.T, self.B
+        for li, (sp, lb) in enumerate(zip(n.layers, n.lbuf)):
+            K, D, k = lb["K"], lb["D"], lb["k"]
+            if train and sp["rnn_drop"] > 0:
+                x_ptr, ldx = self._std_input(n, li)
+                din = self.rnn_drop_in.get((n.arch, li, "x"))
+                self._k("sru_mask_x %dx%d" % (M, K), 0, 8.0 * M * K, "pkc_sru_mask_x", T, B, K,
+                        C.c_void_p(x_ptr), ldx, float(sp["rnn_drop"]), self.seed, ptr(self.ctr),
+                        zlib.crc32(("%s.%d.x" % (n.arch, li)).encode()), ptr(din),
+                        ptr(lb["keep_x"]), ptr(lb["xt"]), s)
+            x_ptr, ldx = self._sru_input(n, li, train)
+            N = D * k
+            self._k("sru_gemm_W %dx%dx%d" % (M, N, K), 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N),
+                    "pkc_gemm", self.prec, 1, 0, M, N, K, C.c_void_p(x_ptr), ldx, ptr(sp["weight"]),
+                    N, ptr(lb["u"]), N, 1, M * N, s)
+            ra = self._sru_args(n, li, train, T)
+            self._k("sru_fwd_loop T=%d n_out=%d" % (T, D), 20.0 * M * D, 4.0 * M * D * (k + 2 + lb["hw"]),
+                    "pkc_sru_fwd", C.byref(ra), s)
+
+    def _sru_bwd(self, n, s, want_dx0=False, on_layer=None):
+        """BPTT of an SruNode, top layer first.  Per layer: the one-launch loop (dU, the highway
+        gradient, d weight_c and d bias), the d weight = X^T dU matmul, then the dX = dU weight^T
+        slabs — folded with the rnn-dropout mask and the highway gradient into ONE slab by
+        pkc_sru_dx when the layer has either."""
+        M, T, B = self.M, self.T, self.B
+        dy_t, dy_ns, dy_stride = self._out_grad(n)
+        dy_ptr = dy_t.data_ptr()
+        for li in reversed(range(len(n.layers))):
+            sp, lb = n.layers[li], n.lbuf[li]
+            K, D, k = lb["K"], lb["D"], lb["k"]
+            N = D * k
+            ra = self._sru_args(n, li, True, T)
+            ra.dy, ra.dy_nslab, ra.dy_slab_stride = dy_ptr, dy_ns, dy_stride
+            ra.dwc, ra.dbias = lb["dwc"][0].data_ptr(), lb["dbias"][0].data_ptr()
+            self._k("sru_bwd_loop T=%d n_out=%d" % (T, D), 40.0 * M * D,
+                    4.0 * M * D * (2 * k + 1 + dy_ns + 2 * lb["hw"]), "pkc_sru_bwd", C.byref(ra), s)
+            x_ptr, ldx = self._sru_input(n, li, True)
+            du = lb["du"].data_ptr()
+            ops = [Op("dWsru %dx%dx%d" % (K, N, M), 2.0 * K * N * M, 4.0 * (M * K + M * N + K * N),
+                      L.GemmProblem(a_kcontig=0, b_kcontig=0, M=K, N=N, K=M, splits=1, A=x_ptr,
+                                    lda=ldx, B=du, ldb=N, C=lb["dweight"][0].data_ptr(), ldc=N,
+                                    slab_stride=0))]
+            nx = n.dx_res if li == 0 else 0
+            want_dx = li > 0 or want_dx0
+            if want_dx:
+                sx = _splits(M, K, N, MAX_SPLITS)
+                dst = lb["dxs"].data_ptr() if lb["one"] else lb["dx"].data_ptr() + 4 * nx * M * K
+                ops.append(Op("dXsru %dx%dx%d" % (M, K, N), 2.0 * M * K * N,
+                              4.0 * (M * N + N * K + sx * M * K),
+                              L.GemmProblem(a_kcontig=1, b_kcontig=1, M=M, N=K, K=N, splits=sx, A=du,
+                                            lda=N, B=sp["weight"].data_ptr(), ldb=N, C=dst, ldc=K,
+                                            slab_stride=M * K)))
+            self._gemms(ops, s)
+            if want_dx and lb["one"]:
+                self._k("sru_dx %dx%d x%d" % (M, K, sx), 0, 4.0 * M * K * (sx + 2), "pkc_sru_dx", T, B,
+                        K, ptr(lb["dxs"]), sx, M * K, ptr(lb["keep_x"]), float(sp["rnn_drop"]),
+                        ptr(lb["dxh"]), C.c_void_p(lb["dx"].data_ptr() + 4 * nx * M * K), s)
+                sx = 1
+            if want_dx:
+                nx += sx
+            if on_layer is not None:
+                on_layer(li)
+            dy_t, dy_ns, dy_stride = lb["dx"], nx, M * K
+            dy_ptr = dy_t.data_ptr()
+            if li == 0 and n.src[0] == "node":
+                n.src[1].gsrc = (lb["dx"], nx, M * K)
+            elif li == 0 and self.want_dx:
+                self._rec_slab_sum_ptr(lb["dx"].data_ptr(), nx, M * K, M * K, self.ext_dx, s)
+
     def _rec_fwd(self, n, s, train):
         if n.std:
             return self._std_fwd(n, s, train)
+        if n.sru:
+            return self._sru_fwd(n, s, train)
         M, T = self.M, self.T
         self._quant_chain(n, s)
         for li, (sp, lb) in enumerate(zip(n.layers, n.lbuf)):
@@ -2323,6 +2464,8 @@ class Engine:
         gradients are queued (the data-parallel bucket cut)."""
         if n.std:
             return self._std_bwd(n, s, want_dx0=want_dx0, on_layer=on_layer)
+        if n.sru:
+            return self._sru_bwd(n, s, want_dx0=want_dx0, on_layer=on_layer)
         M, T = self.M, self.T
         dy_t, dy_ns, dy_stride = self._out_grad(n)
         dy_ptr = dy_t.data_ptr()

@@ -1,6 +1,6 @@
 """pkc.graph — the vocabulary of the cfg [model] graph that pkc.engine executes: the line grammar
 (parse_model, resolve_concat), the loss terms that are not heads (RegTerm, MseTerm), a sentence
-batch (SeqBatch), the graph nodes (Node and its six kinds), the convolution / sinc argument structs
+batch (SeqBatch), the graph nodes (Node and its seven kinds), the convolution / sinc argument structs
 and an architecture's pattern masks.  Nothing here launches a step or reads a kernel-form switch;
 it imports nothing from pkc.engine, which re-exports these names.
 """
@@ -123,6 +123,7 @@ class Node:
     conv = False            # ConvNode: Conv1d + max-pool
     combine = False         # CombineNode: a [model] tensor operation
     std = False             # StdRecNode: torch.nn.LSTM / GRU / RNN cells
+    sru = False             # SruNode: Simple Recurrent Unit layers (one-launch time loops)
     head = False            # a Layer ending in LogSoftmax
     # --- dense fall-through: what a Layer has and the other kinds do not
     W = None                # weight of the engine's own matmul (None: the node has none)
@@ -453,6 +454,40 @@ class StdRecNode(RecNode):
                 if sp["bih"][d] is not None:
                     out.append((sp["bih"][d], ("dbih", li, d), None))
                     out.append((sp["bhh"][d], ("dbhh", li, d), None))
+        return out
+
+
+class SruNode(RecNode):
+    """A whole SRU architecture as one graph node: per layer ONE projection weight (n_in, n_out*k)
+    of both directions, the recurrence vectors weight_c and bias, and the one-launch time loops of
+    pkc_sru_fwd / _bwd.  layer_specs() contract: dict(sru, H, ndir, k, n_in, act, skip, alpha, drop
+    (of the g(c) term), rnn_drop (of the projection's input), weight, weight_c, bias)."""
+    sru = True
+
+    def __init__(self, arch, net, K):
+        self._wire()             # (not RecNode.__init__: no gates of pkc_rnn_args)
+        self.arch, self.net, self.K = arch, net, K
+        self.name = arch
+        self.cell = None                 # none of the pkc_rnn_args cells
+        self.G, self.cand = 1, None
+        self.layers = net.layer_specs()
+        self.N = net.out_dim
+        for sp in self.layers:
+            if sp["act"] not in ("linear", "relu", "tanh"):
+                raise NotImplementedError("%s: activation %s" % (arch, sp["act"]))
+            for key in ("drop", "rnn_drop"):
+                if not 0.0 <= sp[key] < 1.0:
+                    raise ValueError("%s: dropout %s outside [0, 1)" % (arch, sp[key]))
+        if self.layers[0]["n_in"] != K:
+            raise ValueError("%s: built for %d inputs, reads %d" % (arch, self.layers[0]["n_in"], K))
+        self.qw = {}
+        self.emask = {}
+
+    def params(self):
+        out = []
+        for li, sp in enumerate(self.layers):
+            out += [(sp["weight"], ("dweight", li, 0), None), (sp["weight_c"], ("dwc", li, 0), None),
+                    (sp["bias"], ("dbias", li, 0), None)]
         return out
 
 

@@ -1095,3 +1095,114 @@ class RNN_cudnn(_StdRec):
     """neural_networks.py:433-465 (nn.RNN, nonlinearity tanh | relu).  Parameters rnn.0.*."""
     std_cell = "rnn"
     STD_GATES = 1
+
+
+class _SruCell(nn.Module):
+    """One SRU layer's parameters under the names of the published `sru` package's state dict
+    (weight, weight_c, bias, in that order).  The draws are pkc's own, per layer with torch's
+    generator and in this order: weight ~ U(+-sqrt(3 / n_in)); weight_c ~ U(+-sqrt(3)), times
+    sqrt(0.5) with rescale; bias = 0 with the b_r half set to highway_bias."""
+
+    def __init__(self, n_in, n_out, k, rescale, highway_bias):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(n_in, n_out * k))
+        self.weight_c = nn.Parameter(torch.empty(2 * n_out))
+        self.bias = nn.Parameter(torch.zeros(2 * n_out))
+        nn.init.uniform_(self.weight, -math.sqrt(3.0 / n_in), math.sqrt(3.0 / n_in))
+        nn.init.uniform_(self.weight_c, -math.sqrt(3.0), math.sqrt(3.0))
+        with torch.no_grad():
+            if rescale:
+                self.weight_c.mul_(math.sqrt(0.5))
+            self.bias[n_out:].fill_(highway_bias)
+
+
+class _SruHolder(nn.Module):
+    def __init__(self, cells):
+        super().__init__()
+        self.rnn_lst = nn.ModuleList(cells)
+
+
+class SRU(nn.Module):
+    """The Simple Recurrent Unit (Lei et al., EMNLP 2018, the v2 cell with the highway scaling
+    alpha; options per proto/SRU.proto).  A pkc extension: the reference keeps its SRU class
+    commented out and the package it wraps is not runnable here, so the semantics are fixed from the
+    paper (include/pkc.h, pkc_sru_args) and pinned against nothing.  Parameters
+    sru.rnn_lst.<l>.weight (n_in, n_out*k), .weight_c (2 n_out) = [v_f | v_r], .bias (2 n_out) =
+    [b_f | b_r]; k = 4 when the skip term is on and n_in != n_out (layer 0 only), else 3."""
+
+    seq_model = True
+    REFUSED = ("sru_use_selu", "sru_weight_norm", "sru_layer_norm", "sru_is_input_normalized")
+
+    def __init__(self, options, inp_dim):
+        super().__init__()
+        o = options
+        for k in o:
+            if any(w in k for w in ("hcgs", "quant", "prune", "pattern")):
+                raise NotImplementedError("SRU: the key %s (CGS / quantisation / pruning) is not "
+                                          "supported" % k)
+            if "laynorm" in k or "batchnorm" in k:
+                raise NotImplementedError("SRU: the input normalisation key %s is not supported" % k)
+        for k in self.REFUSED:
+            if strtobool(o.get(k, "False")):
+                raise NotImplementedError("SRU: %s = True is not on the pkc path" % k)
+        if int(o.get("sru_n_proj", "0")) != 0:
+            raise NotImplementedError("SRU: sru_n_proj = %s (only 0) is not on the pkc path"
+                                      % o["sru_n_proj"])
+        self.input_dim = inp_dim
+        self.hidden_size = int(o["sru_hidden_size"])
+        self.num_layers = int(o["sru_num_layers"])
+        self.dropout = float(o["sru_dropout"])
+        self.rnn_dropout = float(o["sru_rnn_dropout"])
+        for key, p in (("sru_dropout", self.dropout), ("sru_rnn_dropout", self.rnn_dropout)):
+            if not 0.0 <= p < 1.0:
+                raise ValueError("SRU: %s = %s is outside [0, 1)" % (key, o[key]))
+        # tanh wins if both are set
+        self.act = ("tanh" if strtobool(o["sru_use_tanh"]) else
+                    "relu" if strtobool(o["sru_use_relu"]) else "linear")
+        self.bidirectional = strtobool(o["sru_bidirectional"])
+        self.has_skip_term = strtobool(o["sru_has_skip_term"])
+        self.rescale = strtobool(o["sru_rescale"])
+        self.highway_bias = float(o["sru_highway_bias"])
+        self.alpha = (math.sqrt(1.0 + 2.0 * math.exp(self.highway_bias))
+                      if (self.rescale and self.has_skip_term) else 1.0)
+        self.to_do = o.get("to_do", "train")
+        self.prune = False
+        self.guided_hcgs = False
+        self.apply_guided_hcgs = False
+        self.if_pattern = False
+        self.skip_regularization = False
+        self.out_dim = self.hidden_size * (2 if self.bidirectional else 1)
+        cells, n_in = [], inp_dim
+        for _ in range(self.num_layers):
+            k = 4 if (self.has_skip_term and n_in != self.out_dim) else 3
+            cells.append(_SruCell(n_in, self.out_dim, k, self.rescale, self.highway_bias))
+            n_in = self.out_dim
+        self.sru = _SruHolder(cells)
+
+    def prune_parameters(self):
+        raise NotImplementedError("SRU has no prune hook")
+
+    def forward(self, x):
+        """(T, B, F) -> (T, B, out_dim) on the pkc kernels, trainable under autograd (pkc.plugin)."""
+        return arch_forward(self, x)
+
+    def check_supported(self):
+        pass
+
+    def input_norm_specs(self):
+        return []
+
+    def layer_specs(self):
+        """Per layer: the one projection weight of both directions, the recurrence vectors, the
+        dropout of the layer's g(c) term (drop) and of the projection's input (rnn_drop)."""
+        specs = []
+        for cell in self.sru.rnn_lst:
+            n_in, nk = cell.weight.shape
+            specs.append(dict(sru=True, H=self.hidden_size, ndir=2 if self.bidirectional else 1,
+                              bidir=bool(self.bidirectional), k=nk // self.out_dim, n_in=n_in,
+                              act=self.act, skip=bool(self.has_skip_term), alpha=self.alpha,
+                              drop=self.dropout, rnn_drop=self.rnn_dropout,
+                              weight=cell.weight, weight_c=cell.weight_c, bias=cell.bias,
+                              W=[cell.weight], U=[], bn=False, bnm=[], ln=False, Wmask=None,
+                              Umask=None, ibits=0, qbits=0))
+        return specs

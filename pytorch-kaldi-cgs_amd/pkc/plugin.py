@@ -5,7 +5,7 @@ The reference loads an architecture with ``cls(options, inp_dim)`` (utils.py:176
 F) for a sequence arch — and trains it with ``loss.backward()`` + ``torch.optim`` (core.py:216-232).
 pkc.neural_networks classes keep that contract: their ``forward`` is a torch.autograd.Function whose
 forward and backward are the Engine's HIP layer kernels (pkc_gemm, pkc_dense_fwd/_bwd,
-pkc_rnn_fwd/_bwd, pkc_rnn_std_fwd/_bwd, pkc_conv1d_fwd/_bwd, pkc_conv_post_fwd/_bwd, pkc_sinc_filters_fwd/_bwd,
+pkc_rnn_fwd/_bwd, pkc_rnn_std_fwd/_bwd, pkc_sru_fwd/_bwd, pkc_conv1d_fwd/_bwd, pkc_conv_post_fwd/_bwd, pkc_sinc_filters_fwd/_bwd,
 pkc_logsoftmax_bwd ...) run in the Engine's external mode:
 
   * forward: the masks multiplied into W in place, prune, QuantizeLinear clamp + fake-quantised
