@@ -28,7 +28,8 @@ extern "C" {
  * pkc_combine_args and its three entry points joined under 9 without a bump: no existing struct or
  * entry point changed (tests/test_model_ops_cpu.py checks the new struct's layout).  pkc_rnn_std_args
  * and pkc_rnn_std_fwd / _bwd joined the same way (tests/test_cudnn_cpu.py checks its layout), and so
- * did pkc_sru_args with pkc_sru_fwd / _bwd / _mask_x / _dx (tests/test_sru_cpu.py). */
+ * did pkc_sru_args with pkc_sru_fwd / _bwd / _mask_x / _dx (tests/test_sru_cpu.py) and
+ * pkc_lstmp_args with pkc_lstmp_fwd / _bwd (tests/test_lstmp_cpu.py). */
 #define PKC_ABI_VERSION 9
 
 enum { PKC_OK = 0, PKC_ERR_ARG = -1, PKC_ERR_HIP = -2, PKC_ERR_IO = -3, PKC_ERR_UNSUPPORTED = -4 };
@@ -670,6 +671,61 @@ typedef struct {
 } pkc_rnn_std_args;
 int pkc_rnn_std_fwd(const pkc_rnn_std_args* a, void* stream);
 int pkc_rnn_std_bwd(const pkc_rnn_std_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Projected LSTM (LSTMP; Sak et al., Interspeech 2014): the time loops of LSTM_cudnn with
+ * proj_size = P, i.e. torch.nn.LSTM(..., proj_size=P), 0 < P < H, zero initial state.  Additive to
+ * ABI 9: a new struct and new entry points only (pkc_rnn_std_args is untouched).  One layer, both
+ * directions; direction d (1: reverse, walks time T-1 .. 0) has its own operands and is a grid
+ * dimension of every step launch.
+ *   wpre[d] (T, B, 4H), rows in natural time: the packed input projection weight_ih x + bias_ih;
+ *   U[d]    (4H, P): weight_hh as torch packs it, gate rows i,f,g,o;
+ *   bhh[d]  (4H): bias_hh, or NULL (bias = False).  The step adds it to the recurrent product;
+ *   Whr[d]  (P, H): weight_hr, the recurrent projection (no bias).
+ * Cell (a = wpre, u = U h_{t-1} + bhh):
+ *   i,f,o = sig(a + u), g = tanh(a_g + u_g), c = f c_{t-1} + i g, ht = o tanh(c)   (H wide)
+ *   h = Whr ht                                                                      (P wide)
+ * h is both the layer output and the recurrent state.  U Whr is never folded into one matrix.
+ * Forward: two dependent launches per time step (the cell update, skipping the product at step
+ * 0; the projection).  Saves hs (ndir, T+1, B, P) and cs (ndir, T+1, B, H) in the slot layout of
+ * pkc_rnn_std_args — direction 0 keeps the state after time t in slot t+1 (slot 0 = the zero
+ * initial state), direction 1 in slot t (slot T = 0), so that h_{t-1} of the T steps are T
+ * consecutive slots in natural time —, the gate activations gates (ndir, T, B, 4H), the
+ * unprojected ht (ndir, T, B, H) that the weight_hr gradient contracts with, and writes the layer
+ * output y (T, B, ndir*P).  Inter-layer dropout (train != 0 and drop_p > 0; the caller passes
+ * drop_p = 0 for the last layer): y = h keep / (1 - p) with keep ~ Bernoulli(1 - p) per element of
+ * y, drawn from the counter-hash stream of pkc_dense_fwd (index = the element's flat index in y) or
+ * read from keep_in; keep (u8, the layout of y) is written for the backward.  hs stays undropped.
+ * Backward (pkc_lstmp_bwd): dy = dL/dy as dy_nslab partial slabs.  U and Whr are transposed once
+ * per call, then two dependent launches per step, last step first:
+ *   dhp_t = (sum of the dy slabs) keep / (1 - p) + dgates_{next step} U      (over 4H; not at the
+ *           first BPTT step), the total gradient arriving at h_t: dhp (ndir, T, B, P), natural time;
+ *   dht_t = dhp_t Whr (over P), then the LSTM gate gradients with the dc f carry: dgates
+ *           (ndir, T, B, 4H), natural time, the gradients of the pre-activations.
+ * So per direction, all plain matmuls over the T*B rows:
+ *   d weight_ih = dgates^T x, d bias_ih = d bias_hh = colsum dgates, dx += dgates weight_ih,
+ *   d weight_hh = dgates^T h_{t-1} (4H x P), d weight_hr = dhp^T ht (P x H).
+ * Caller-provided scratch: ut (ndir, P, 4H) floats (the transposed weight_hh), wt (ndir, H, P)
+ * floats (the transposed weight_hr), work (ndir, B, H) floats (the dc f carries).
+ * No atomics: reruns are bit-identical, and a bidirectional call equals two one-direction calls.
+ * PKC_ERR_ARG with a pkc_last_error() text for a null pointer, P <= 0, P >= H, H > 2048, ndir not
+ * 1 or 2, or drop_p outside [0, 1).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  int T, B, H, P, ndir, train;
+  const float* wpre[2];
+  const float* U[2];
+  const float* bhh[2];
+  const float* Whr[2];
+  float* hs; float* cs; float* gates; float* ht; float* y;
+  float drop_p; uint64_t seed; const int64_t* step_ctr; int64_t stream_id;
+  const uint8_t* keep_in;      /* optional injected keep mask (T, B, ndir*P) */
+  uint8_t* keep;               /* (T, B, ndir*P) mask in use */
+  const float* dy; int dy_nslab; int64_t dy_slab_stride;
+  float* dgates; float* dhp; float* ut; float* wt; float* work;
+} pkc_lstmp_args;
+int pkc_lstmp_fwd(const pkc_lstmp_args* a, void* stream);
+int pkc_lstmp_bwd(const pkc_lstmp_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Simple Recurrent Unit (Lei et al., EMNLP 2018, the v2 cell with the highway scaling alpha): the

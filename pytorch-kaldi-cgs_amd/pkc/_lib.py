@@ -167,6 +167,18 @@ class RnnStdArgs(C.Structure):
                 ("dgates", vp), ("ut", vp), ("work", vp)]
 
 
+# include/pkc.h pkc_lstmp_args: the time loops of the projected LSTM (LSTM_cudnn, proj_size > 0)
+class LstmpArgs(C.Structure):
+    _fields_ = [("T", C.c_int), ("B", C.c_int), ("H", C.c_int), ("P", C.c_int),
+                ("ndir", C.c_int), ("train", C.c_int),
+                ("wpre", vp * 2), ("U", vp * 2), ("bhh", vp * 2), ("Whr", vp * 2),
+                ("hs", vp), ("cs", vp), ("gates", vp), ("ht", vp), ("y", vp),
+                ("drop_p", C.c_float), ("seed", C.c_uint64), ("step_ctr", vp), ("stream_id", i64),
+                ("keep_in", vp), ("keep", vp),
+                ("dy", vp), ("dy_nslab", C.c_int), ("dy_slab_stride", i64),
+                ("dgates", vp), ("dhp", vp), ("ut", vp), ("wt", vp), ("work", vp)]
+
+
 # include/pkc.h pkc_sru_args: the one-launch time loop of an SRU layer
 class SruArgs(C.Structure):
     _fields_ = [("T", C.c_int), ("B", C.c_int), ("d", C.c_int), ("ndir", C.c_int), ("k", C.c_int),
@@ -187,6 +199,8 @@ _SIGS = {
     "pkc_sru_dx": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, C.c_int, i64, vp, C.c_float, vp, vp, vp]),
     "pkc_rnn_std_fwd": (C.c_int, [C.POINTER(RnnStdArgs), vp]),
     "pkc_rnn_std_bwd": (C.c_int, [C.POINTER(RnnStdArgs), vp]),
+    "pkc_lstmp_fwd": (C.c_int, [C.POINTER(LstmpArgs), vp]),
+    "pkc_lstmp_bwd": (C.c_int, [C.POINTER(LstmpArgs), vp]),
     "pkc_combine_ok": (C.c_int, [C.POINTER(CombineArgs), C.c_int]),
     "pkc_combine_fwd": (C.c_int, [C.POINTER(CombineArgs), vp]),
     "pkc_combine_bwd": (C.c_int, [C.POINTER(CombineArgs), vp]),

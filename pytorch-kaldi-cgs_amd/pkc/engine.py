@@ -837,22 +837,28 @@ class Engine:
         n.dx_res = len(n.src[1].mse_grad) if n.src[0] == "node" else 0
         for sp in n.layers:
             H, nd = sp["H"], sp["ndir"]
-            D = nd * H
+            P = sp.get("P", 0)                   # projected LSTM (pkc_lstmp_args): state width P
+            R = P or H
+            D = nd * R
             xres = 0 if n.lbuf else n.dx_res
             nx = nd * (2 if n.std_cell == "gru" else 1) * MAX_SPLITS      # dX slab groups
-            lb = dict(K=K, H=H, B2=nd * B, D=D, nd=nd,
+            lb = dict(K=K, H=H, P=P, R=R, B2=nd * B, D=D, nd=nd,
                       zslab=_f32(MAX_SPLITS * M * G * H, dev), wpre=_f32(nd * M * G * H, dev),
                       work=_f32(L.lib().pkc_dense_work_size(M, G * H), dev),
-                      hs=_f32(nd * (T + 1) * B * H, dev),
+                      hs=_f32(nd * (T + 1) * B * R, dev),
                       cs=_f32(nd * (T + 1) * B * H, dev) if n.std_cell == "lstm" else None,
                       un=_f32(nd * M * H, dev) if n.std_cell == "gru" else None,
+                      ht=_f32(nd * M * H, dev) if P else None,
                       gates=_f32(nd * M * G * H, dev), y=_f32(M * D, dev),
                       keep=(torch.zeros(M * D, dtype=torch.uint8, device=dev)
                             if sp["drop"] > 0 else None),
-                      dgates=_f32(nd * M * GD * H, dev), ut=_f32(nd * H * G * H, dev),
+                      dgates=_f32(nd * M * GD * H, dev), ut=_f32(nd * R * G * H, dev),
+                      dhp=_f32(nd * M * P, dev) if P else None,
+                      wt=_f32(nd * H * P, dev) if P else None,
                       rwork=_f32(nd * 2 * B * H, dev), dbt=_f32(nd * GD * H, dev),
                       dx=_f32((nx + xres) * M * K, dev),
-                      dW=[None] * nd, dU=[None] * nd, dbih=[None] * nd, dbhh=[None] * nd)
+                      dW=[None] * nd, dU=[None] * nd, dbih=[None] * nd, dbhh=[None] * nd,
+                      dWhr=[None] * nd)
             n.lbuf.append(lb)
             K = D
         n.rslab = None
@@ -1755,16 +1761,24 @@ class Engine:
     def _std_args(self, n, li, train, T):
         sp, lb = n.layers[li], n.lbuf[li]
         H, nd, M = lb["H"], lb["nd"], T * self.B
-        a = L.RnnStdArgs()
-        a.cell, a.T, a.B, a.H, a.ndir = n.cid, T, self.B, H, nd
-        a.act, a.train = L.ACT[sp["act"]], int(train)
+        if lb["P"]:                          # projected LSTM: pkc_lstmp_args
+            a = L.LstmpArgs()
+            a.T, a.B, a.H, a.P, a.ndir, a.train = T, self.B, H, lb["P"], nd, int(train)
+            a.ht, a.dhp, a.wt = lb["ht"].data_ptr(), lb["dhp"].data_ptr(), lb["wt"].data_ptr()
+            a.cs = lb["cs"].data_ptr()
+        else:
+            a = L.RnnStdArgs()
+            a.cell, a.T, a.B, a.H, a.ndir = n.cid, T, self.B, H, nd
+            a.act, a.train = L.ACT[sp["act"]], int(train)
+            a.cs = lb["cs"].data_ptr() if lb["cs"] is not None else None
+            a.un = lb["un"].data_ptr() if lb["un"] is not None else None
         for d in range(nd):
             a.wpre[d] = lb["wpre"].data_ptr() + 4 * d * M * n.G * H
             a.U[d] = sp["U"][d].data_ptr()
             a.bhh[d] = sp["bhh"][d].data_ptr() if sp["bhh"][d] is not None else None
+            if lb["P"]:
+                a.Whr[d] = sp["Whr"][d].data_ptr()
         a.hs = lb["hs"].data_ptr()
-        a.cs = lb["cs"].data_ptr() if lb["cs"] is not None else None
-        a.un = lb["un"].data_ptr() if lb["un"] is not None else None
         a.gates, a.y = lb["gates"].data_ptr(), lb["y"].data_ptr()
         a.drop_p = float(sp["drop"])
         a.seed = self.seed
@@ -1805,6 +1819,12 @@ class Engine:
                 self._k("rnn_std_bias H=%d" % H, 0, 4.0 * M * GH * (sf + 1), "pkc_dense_fwd",
                         C.byref(a), ptr(lb["work"]), s)
             ra = self._std_args(n, li, train, T)
+            R = lb["R"]
+            if lb["P"]:     # two launches per step: U h_{t-1} over P, weight_hr ht over H
+                self._k("lstmp_fwd_loop T=%d H=%d P=%d" % (T, H, R),
+                        2.0 * T * lb["B2"] * (GH + H) * R, 4.0 * T * lb["nd"] * (GH + H) * R,
+                        "pkc_lstmp_fwd", C.byref(ra), s)
+                continue
             self._k("rnn_std_fwd_loop T=%d H=%d" % (T, H), 2.0 * T * lb["B2"] * GH * H,
                     4.0 * T * lb["nd"] * GH * H, "pkc_rnn_std_fwd", C.byref(ra), s)
 
@@ -1826,15 +1846,21 @@ class Engine:
                 self._rec_slab_sum_ptr(dy_ptr, dy_ns, M * lb["D"], dy_stride, n.dysum, s)
                 dy_ptr, dy_ns, dy_stride = n.dysum.data_ptr(), 1, M * lb["D"]
             ra.dy, ra.dy_nslab, ra.dy_slab_stride = dy_ptr, dy_ns, dy_stride
-            self._k("rnn_std_bwd_loop T=%d H=%d" % (T, H), 2.0 * T * lb["B2"] * GH * H,
-                    4.0 * T * nd * GH * H, "pkc_rnn_std_bwd", C.byref(ra), s)
+            P, R = lb["P"], lb["R"]
+            if P:
+                self._k("lstmp_bwd_loop T=%d H=%d P=%d" % (T, H, P),
+                        2.0 * T * lb["B2"] * (GH + H) * P, 4.0 * T * nd * (GH + H) * P,
+                        "pkc_lstmp_bwd", C.byref(ra), s)
+            else:
+                self._k("rnn_std_bwd_loop T=%d H=%d" % (T, H), 2.0 * T * lb["B2"] * GH * H,
+                        4.0 * T * nd * GH * H, "pkc_rnn_std_bwd", C.byref(ra), s)
             x_ptr, ldx = self._std_input(n, li)
             wg, tail, dxp = [], [], []
             nx = n.dx_res if li == 0 else 0
             want_dx = li > 0 or want_dx0
             for d in range(nd):
                 dg = lb["dgates"].data_ptr() + 4 * d * M * GDH
-                hp = lb["hs"].data_ptr() + 4 * (d * (T + 1) + d) * B * H     # h_{t-1}, natural time
+                hp = lb["hs"].data_ptr() + 4 * (d * (T + 1) + d) * B * R     # h_{t-1}, natural time
                 dW, dU = lb["dW"][d].data_ptr(), lb["dU"][d].data_ptr()
                 # input-side column ranges of the gate-gradient rows -> weight_ih row ranges
                 # (GRU rows [r, z, n_rec, n_in]: r, z and n_in; else all G gates)
@@ -1855,10 +1881,17 @@ class Engine:
                                                     C=lb["dx"].data_ptr() + 4 * nx * M * K, ldc=K,
                                                     slab_stride=M * K)))
                         nx += sx
-                wg.append(Op("dWhh%d %dx%dx%d" % (d, GH, H, M), 2.0 * GH * H * M,
-                             4.0 * (M * GH + M * H + GH * H),
-                             L.GemmProblem(a_kcontig=0, b_kcontig=0, M=GH, N=H, K=M, splits=1, A=dg,
-                                           lda=GDH, B=hp, ldb=H, C=dU, ldc=H, slab_stride=0)))
+                wg.append(Op("dWhh%d %dx%dx%d" % (d, GH, R, M), 2.0 * GH * R * M,
+                             4.0 * (M * GH + M * R + GH * R),
+                             L.GemmProblem(a_kcontig=0, b_kcontig=0, M=GH, N=R, K=M, splits=1, A=dg,
+                                           lda=GDH, B=hp, ldb=R, C=dU, ldc=R, slab_stride=0)))
+                if P:       # d weight_hr = dhp^T ht, both in natural time
+                    wg.append(Op("dWhr%d %dx%dx%d" % (d, P, H, M), 2.0 * P * H * M,
+                                 4.0 * (M * P + M * H + P * H),
+                                 L.GemmProblem(a_kcontig=0, b_kcontig=0, M=P, N=H, K=M, splits=1,
+                                               A=lb["dhp"].data_ptr() + 4 * d * M * P, lda=P,
+                                               B=lb["ht"].data_ptr() + 4 * d * M * H, ldb=H,
+                                               C=lb["dWhr"][d].data_ptr(), ldc=H, slab_stride=0)))
                 if lb["dbih"][d] is not None:
                     # column sums of the whole gate-gradient rows, then the two biases' ranges
                     # (bias_hh: the recurrent side — for the GRU's b_hn, sum r da_n)

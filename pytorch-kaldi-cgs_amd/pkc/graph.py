@@ -421,7 +421,9 @@ class StdRecNode(RecNode):
     graph node: per layer and direction a packed weight_ih (G*H, K), weight_hh (G*H, H) and the two
     biases, the standard-cell time loops of pkc_rnn_std_fwd / _bwd, dropout between layers.
     layer_specs() contract: dict(std, H, act, bidir, ndir, drop (of the layer's output; 0 on the
-    last), W / U / bih / bhh: one entry per direction (biases None without bias))."""
+    last), W / U / bih / bhh: one entry per direction (biases None without bias)).  The projected
+    LSTM (LSTM_cudnn with proj_size = P) adds P and Whr (weight_hr (P, H) per direction): its
+    weight_hh is (4H, P), its output ndir * P wide and its time loops pkc_lstmp_fwd / _bwd."""
     std = True
 
     def __init__(self, arch, net, K):
@@ -442,6 +444,9 @@ class StdRecNode(RecNode):
                 raise NotImplementedError("%s: nonlinearity %s (tanh or relu)" % (arch, sp["act"]))
             if not 0.0 <= sp["drop"] < 1.0:
                 raise ValueError("%s: dropout %s outside [0, 1)" % (arch, sp["drop"]))
+            if sp.get("P") and not (net.std_cell == "lstm" and 0 < sp["P"] < sp["H"]):
+                raise ValueError("%s: proj_size %s (LSTM only, 0 < proj_size < hidden_size = %d)"
+                                 % (arch, sp["P"], sp["H"]))
         self.qw = {}
         self.emask = {}
 
@@ -454,6 +459,8 @@ class StdRecNode(RecNode):
                 if sp["bih"][d] is not None:
                     out.append((sp["bih"][d], ("dbih", li, d), None))
                     out.append((sp["bhh"][d], ("dbhh", li, d), None))
+                if sp.get("P"):
+                    out.append((sp["Whr"][d], ("dWhr", li, d), None))
         return out
 
 

@@ -985,19 +985,23 @@ class _StdParams(nn.Module):
     ..._l1, ...) and with nn.RNNBase.reset_parameters' draws (U(-1/sqrt(H), 1/sqrt(H)) in that
     order).  Plain Parameters, not a wrapped nn.LSTM: its flatten_parameters() may re-seat the
     parameter storage on .to(device), while the engine keeps device pointers, and its own forward
-    (MIOpen) must never run."""
+    (MIOpen) must never run.  proj > 0 (nn.LSTM's proj_size): weight_hh is (G*H, proj), the layers
+    above the first read ndir * proj inputs and weight_hr (proj, H) follows the biases."""
 
-    def __init__(self, G, inp, H, layers, bias, ndir):
+    def __init__(self, G, inp, H, layers, bias, ndir, proj=0):
         super().__init__()
+        R = proj if proj > 0 else H              # the width of the recurrent state
         for l in range(layers):
-            K = inp if l == 0 else H * ndir
+            K = inp if l == 0 else R * ndir
             for d in range(ndir):
                 sfx = "_l%d%s" % (l, "_reverse" if d else "")
                 self.register_parameter("weight_ih" + sfx, nn.Parameter(torch.empty(G * H, K)))
-                self.register_parameter("weight_hh" + sfx, nn.Parameter(torch.empty(G * H, H)))
+                self.register_parameter("weight_hh" + sfx, nn.Parameter(torch.empty(G * H, R)))
                 if bias:
                     self.register_parameter("bias_ih" + sfx, nn.Parameter(torch.empty(G * H)))
                     self.register_parameter("bias_hh" + sfx, nn.Parameter(torch.empty(G * H)))
+                if proj > 0:
+                    self.register_parameter("weight_hr" + sfx, nn.Parameter(torch.empty(proj, H)))
         stdv = 1.0 / math.sqrt(H) if H > 0 else 0
         for p in self.parameters():
             nn.init.uniform_(p, -stdv, stdv)
@@ -1008,7 +1012,10 @@ class _StdRec(nn.Module):
     proto/{LSTM,GRU,RNN}_cudnn.proto): torch.nn.LSTM / GRU / RNN with a zero initial state.  Each
     direction has its own weights, the GRU is torch's cell (the reset gate multiplies after the
     recurrent product), and dropout acts between layers — the standard-cell time loops of
-    pkc_rnn_std_fwd / _bwd, not the cells of the reference's own LSTM / GRU / RNN classes."""
+    pkc_rnn_std_fwd / _bwd, not the cells of the reference's own LSTM / GRU / RNN classes.
+    LSTM_cudnn also reads torch's own keyword proj_size (default 0): with 0 < proj_size <
+    hidden_size it is the projected LSTM, torch.nn.LSTM(..., proj_size=P), on the time loops of
+    pkc_lstmp_fwd / _bwd (the reference class forwards no proj_size; the pin is torch's)."""
 
     seq_model = True
     std_cell = ""           # "lstm" | "gru" | "rnn": also the attribute holding the parameters
@@ -1033,6 +1040,13 @@ class _StdRec(nn.Module):
         self.bidirectional = strtobool(o["bidirectional"])
         if not 0.0 <= self.dropout < 1.0:
             raise ValueError("%s: dropout = %s is outside [0, 1)" % (name, o["dropout"]))
+        self.proj_size = int(o.get("proj_size", 0))
+        if self.proj_size < 0 or self.proj_size >= self.hidden_size:
+            raise ValueError("%s: proj_size = %s has to be a non-negative integer smaller than "
+                             "hidden_size = %d" % (name, o["proj_size"], self.hidden_size))
+        if self.proj_size != 0 and self.std_cell != "lstm":
+            raise ValueError("%s: proj_size = %s, but proj_size is only supported by LSTM_cudnn"
+                             % (name, o["proj_size"]))
         self.nonlinearity = "tanh"
         if self.std_cell == "rnn":
             self.nonlinearity = o["nonlinearity"]
@@ -1046,8 +1060,9 @@ class _StdRec(nn.Module):
         self.skip_regularization = strtobool(o.get("skip_regularization", "False"))
         nd = 2 if self.bidirectional else 1
         setattr(self, self.std_cell, nn.ModuleList([_StdParams(
-            self.STD_GATES, inp_dim, self.hidden_size, self.num_layers, self.bias, nd)]))
-        self.out_dim = self.hidden_size * nd
+            self.STD_GATES, inp_dim, self.hidden_size, self.num_layers, self.bias, nd,
+            self.proj_size)]))
+        self.out_dim = (self.proj_size or self.hidden_size) * nd
 
     def prune_parameters(self):
         raise NotImplementedError("the reference %s has no prune hook" % type(self).__name__)
@@ -1076,6 +1091,8 @@ class _StdRec(nn.Module):
                               drop=self.dropout if l < self.num_layers - 1 else 0.0,
                               W=get("weight_ih"), U=get("weight_hh"), bih=get("bias_ih"),
                               bhh=get("bias_hh"), Wmask=None, Umask=None, ibits=0, qbits=0))
+            if self.proj_size:
+                specs[-1].update(P=self.proj_size, Whr=get("weight_hr"))
         return specs
 
 
