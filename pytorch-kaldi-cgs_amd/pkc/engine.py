@@ -176,6 +176,61 @@ def persist_plans(mask):
     return out
 
 
+def rnn_kmaps(masks, cand, mode="auto"):
+    """Block-sparse tables of the recurrent step kernels (pkc_rnn_args.kmap_*) for static U masks:
+    masks the per-gate H x H masks (nonzero = kept), cand the candidate gate of a two-phase cell
+    (GRU, minimalGRU) or None, mode "auto" (a table only when it cuts the contraction below the
+    dense strip), "force" (whenever a tile's blocks fit in 64 slots) or "off".  Per step-kernel tile
+    the 16-wide contraction blocks that hold a nonzero of the mask, -1 behind them.  Returns
+    (kmap_fwd, kmap_s_fwd, kmap_bwd, kmap_s_bwd): CPU int32 tensors [tiles, S], or (None, 0) for a
+    table that does not apply."""
+    if mode == "off":
+        return None, 0, None, 0
+    G = len(masks)
+    H = masks[0].shape[0]
+    nb = -(-H // 16)
+    rowp, pres = [], []
+    for m in masks:
+        mb = torch.zeros(nb * 16, nb * 16)
+        mb[:H, :H] = (torch.as_tensor(m).detach().reshape(H, H) != 0).float().cpu()
+        rowp.append(mb.view(nb * 16, nb, 16).amax(2) > 0)          # [row][col blk]
+        pres.append(mb.view(nb, 16, nb, 16).amax(dim=(1, 3)) > 0)  # [row blk][col blk]
+
+    def fwd_tiles(gates):
+        """[tile][k blk] of the forward tiles holding `gates` of 16 / len(gates) units"""
+        NU = 16 // len(gates)
+        nt = -(-H // NU)
+        acc = torch.zeros(nt * NU, nb, dtype=torch.bool)
+        for g in gates:
+            acc[:H] |= rowp[g][:H]
+        return acc.view(nt, NU, nb).any(1)
+
+    if cand is None:
+        fwd = fwd_tiles(range(G))
+    else:
+        # two-phase cells: the phase-0 table (the gates that read h_{t-1}) and then the
+        # phase-1 table (the candidate gate, 16 units a tile) in one allocation
+        fwd = torch.cat([fwd_tiles([g for g in range(G) if g != cand]), fwd_tiles([cand])])
+    nt = fwd.shape[0]
+    # BPTT tile (gate g, columns k-block kt) reads the row blocks j with a nonzero
+    bwd = torch.stack([p_.t() for p_ in pres])          # [g][kt][j blk]
+    dense_s = 16 if H <= 256 else 32 if H <= 512 else 48 if H <= 768 else 64 if H <= 1024 else 128
+
+    def table(presence, rows):
+        kept = int(presence.sum(-1).max().item())
+        S = next((c for c in (16, 32, 64) if c >= kept), None)
+        if S is None or (mode != "force" and S >= dense_s):
+            return None, 0
+        tab = torch.full((rows, S), -1, dtype=torch.int32)
+        pc = presence.reshape(rows, -1)
+        for i in range(rows):
+            idx = torch.nonzero(pc[i]).flatten()
+            tab[i, :len(idx)] = idx.to(torch.int32)
+        return tab, S
+
+    return table(fwd, nt) + table(bwd, G * nb)
+
+
 def _splits(M, N, K, cap):
     return max(1, min(cap, L.lib().pkc_gemm_pick_splits(M, N, K)))
 
@@ -1028,48 +1083,10 @@ class Engine:
                 if any(m is None or id(U) in n.emask for m, U in zip(um, sp["U"])):
                     continue
                 H = lb["H"]
-                nb = -(-H // 16)
-                rowp, pres = [], []
-                for m in um:
-                    mb = torch.zeros(nb * 16, nb * 16, device=self.dev)
-                    mb[:H, :H] = (m.detach().reshape(H, H) != 0).float()
-                    rowp.append(mb.view(nb * 16, nb, 16).amax(2) > 0)          # [row][col blk]
-                    pres.append(mb.view(nb, 16, nb, 16).amax(dim=(1, 3)) > 0)  # [row blk][col blk]
-                def fwd_tiles(gates):
-                    """[tile][k blk] of the forward tiles holding `gates` of 16 / len(gates) units"""
-                    NU = 16 // len(gates)
-                    nt = -(-H // NU)
-                    acc = torch.zeros(nt * NU, nb, dtype=torch.bool, device=self.dev)
-                    for g in gates:
-                        acc[:H] |= rowp[g][:H]
-                    return acc.view(nt, NU, nb).any(1)
-
-                if n.cand is None:
-                    fwd = fwd_tiles(range(n.G))
-                else:
-                    # two-phase cells: the phase-0 table (the gates that read h_{t-1}) and then the
-                    # phase-1 table (the candidate gate, 16 units a tile) in one allocation
-                    fwd = torch.cat([fwd_tiles([g for g in range(n.G) if g != n.cand]),
-                                     fwd_tiles([n.cand])])
-                nt = fwd.shape[0]
-                # BPTT tile (gate g, columns k-block kt) reads the row blocks j with a nonzero
-                bwd = torch.stack([p_.t() for p_ in pres])          # [g][kt][j blk]
-                dense_s = 16 if H <= 256 else 32 if H <= 512 else 48 if H <= 768 else 64 if H <= 1024 else 128
-
-                def table(presence, rows):
-                    kept = int(presence.sum(-1).max().item())
-                    S = next((c for c in (16, 32, 64) if c >= kept), None)
-                    if S is None or (RNN_SPARSE != "force" and S >= dense_s):
-                        return None, 0
-                    tab = torch.full((rows, S), -1, dtype=torch.int32)
-                    pc = presence.reshape(rows, -1).cpu()
-                    for i in range(rows):
-                        idx = torch.nonzero(pc[i]).flatten()
-                        tab[i, :len(idx)] = idx.to(torch.int32)
-                    return tab.to(self.dev), S
-
-                lb["kmap_fwd"], lb["kmap_s_fwd"] = table(fwd, nt)
-                lb["kmap_bwd"], lb["kmap_s_bwd"] = table(bwd, n.G * nb)
+                kf, sf, kb, sb = rnn_kmaps([m.detach().reshape(H, H) for m in um], n.cand,
+                                           RNN_SPARSE)
+                lb["kmap_fwd"], lb["kmap_s_fwd"] = (kf.to(self.dev) if kf is not None else None), sf
+                lb["kmap_bwd"], lb["kmap_s_bwd"] = (kb.to(self.dev) if kb is not None else None), sb
                 lb["persist_fwd"] = lb["persist_bwd"] = None
                 if (RNN_PERSIST and n.cell == L.CELL_LIGRU and self.prec == L.PREC_BF16
                         and lb.get("hs_h") is not None):

@@ -2,9 +2,14 @@
 the C ABI, every buffer in the layout include/pkc.h documents (fields as Engine._rnn_args fills
 them), every buffer the kernels write between sentinel guards.  Also the host-side mirror of the
 step kernels' dispatch (step_form) and the table of cases tests/test_gpu_rnn_kernels.py runs, so the
-CPU suite can check what the table reaches without a GPU (tests/test_oracle_steps_cpu.py)."""
+CPU suite can check what the table reaches without a GPU (tests/test_oracle_steps_cpu.py).  The
+block-sparse step kernels and the persistent liGRU loops take a U mask and the tables of
+pkc.engine.rnn_kmaps / persist_plans (Layer's umask / kmaps / plans); their dispatch mirror
+(sparse_step_form), masks and case tables are the second half of the tables section, run by
+tests/test_gpu_rnn_sparse_kernels.py and checked on the CPU by tests/test_rnn_tables_cpu.py."""
 import collections
 import ctypes as C
+import functools
 
 import torch
 
@@ -51,8 +56,9 @@ Case.B2 = property(lambda c: 2 * c.B if c.bidir else c.B)
 Case.id = property(lambda c: "%s-T%d-H%d-B2_%d-%s%s" % (
     c.cell, c.T, c.H, c.B2, c.act, "-slabs%d" % c.nslab if c.nslab > 1 else ""))
 
-ROWS_OF = {3: (3, False), 6: (3, True), 12: (6, True), 16: (16, False), 17: (17, False),
-           20: (10, True), 32: (16, True), 34: (17, True)}        # B2 -> (B, bidir)
+ROWS_OF = {1: (1, False), 2: (1, True), 3: (3, False), 6: (3, True), 12: (6, True),
+           16: (16, False), 17: (17, False), 20: (10, True), 32: (16, True),
+           34: (17, True)}                                        # B2 -> (B, bidir)
 H_CLASSES = {16: (5, 250, 256), 32: (257, 510, 512), 48: (513, 550, 768), 64: (769, 770, 1024),
              128: (1025, 1030, 2048)}
 # per strip class: the B2 of its three H values (vw 1, 2, 4) — one of each row-tiling class, in an
@@ -111,6 +117,232 @@ def grid_cases():
         out += [(make_case("lstm", 4, H, B2, "tanh", seed=40100 + 10 * bf + i), bf)
                 for i, (H, B2) in enumerate(((512, 6), (768, 20), (1024, 32)))]
     return out
+
+
+# ------------------------------------------------------------------ block-sparse and persistent
+def sparse_step_form(cell, H, B2, slots, bf16=False):
+    """fwd_impl_s / bwd_impl_s with SP = true (a kmap table of `slots` slots per tile): S = slots
+    whatever H is, 4 waves always (step_waves<S, true>), 16-row tiles up to B2 = 16, the load width
+    from H alone.  bf16 (BF && SP): liGRU and LSTM only (check() refuses the RNN, the two-phase
+    cells have no bf16 steps)."""
+    assert cell in CELLS and 0 < H <= 2048 and B2 > 0 and slots in (16, 32, 64)
+    assert not bf16 or cell in ("ligru", "lstm")
+    rows = 16 if B2 <= 16 else 32
+    vw = 4 if H % 4 == 0 else 2 if H % 2 == 0 else 1
+    load = ("h8" if H % 8 == 0 else "h2" if H % 2 == 0 else "h1") if bf16 else vw
+    return slots, 4, rows, (B2 + rows - 1) // rows, load
+
+
+CAND = {"gru": 2, "mingru": 1}          # the two-phase cells' candidate gate
+
+
+def block_mask(H, keep, seed, G=1, thin=0.5, bs=16):
+    """G masks (G, H, H) bool of random bs x bs blocks, each kept with probability `keep`; inside a
+    kept block every element but the first stays with probability `thin` (the tables must list a
+    block for one nonzero)."""
+    g = torch.Generator().manual_seed(seed)
+    nb = -(-H // bs)
+    blocks = torch.rand(G, nb, nb, generator=g) < keep
+    m = blocks.repeat_interleave(bs, 1).repeat_interleave(bs, 2)[:, :H, :H].clone()
+    first = torch.zeros(G, H, H, dtype=torch.bool)
+    first[:, ::bs, ::bs] = True
+    return m & ((torch.rand(G, H, H, generator=g) < thin) | first)
+
+
+def hcgs_mask(H, seed, blocks=(32, 2), drops=(75, 75)):
+    """(1, H, H) bool HCGS mask (oracle.masks.hcgs_conn_mat, C3's [32, 2] / [75, 75] by default)."""
+    import numpy as np
+    from oracle import masks as OM
+    m = OM.hcgs_conn_mat(H, H, list(blocks), list(drops), np.random.RandomState(seed))
+    return torch.from_numpy(m != 0)[None]
+
+
+def _plans(mask):
+    from pkc import engine as E
+    return E.persist_plans(mask.any(0).numpy())
+
+
+def plan_stats(plan, nw):
+    """(fragments, run = the longest wave's valid slots, cut tiles, waves with no slot) of one plan."""
+    tab = plan.reshape(nw, -1)
+    valid = (tab >> 17) & 1
+    return (int(valid.sum()), int(valid.sum(1).max()), int((valid & (tab >> 18) & 1).sum()),
+            int((valid.sum(1) == 0).sum()))
+
+
+def _search(make, ok, tries=4000):
+    for s in range(tries):
+        m = make(s)
+        if ok(m):
+            return m
+    raise AssertionError("no mask found in %d seeds" % tries)
+
+
+@functools.lru_cache(maxsize=None)
+def _persist_mask(kind, H, seed):
+    """(1, H, H) bool masks for the persistent liGRU loops' plan classes (one mask for both gates, as
+    the plan is the union's).  Seeded searches take the first seed whose plans (pkc.engine.
+    persist_plans) have the property; the searches read the geometry, never a kernel's output."""
+    from pkc import engine as E
+    nw, nsf, nsb = E.persist_geometry()[:3]
+    if kind == "dense":
+        return torch.ones(1, H, H, dtype=torch.bool)
+    if kind == "blocks":
+        return _search(lambda s: block_mask(H, 0.6, seed + s), lambda m: _plans(m) is not None)
+    if kind == "c3":            # a C3-like HCGS mask whose plans fit the slots
+        return _search(lambda s: hcgs_mask(H, seed + s), lambda m: _plans(m) is not None)
+
+    def run_is(which, want):
+        def ok(m):
+            p = _plans(m)               # (once per mask)
+            return p is not None and plan_stats(p[which], nw)[1] == want
+        return ok
+    if kind == "slots_fwd":     # forward run == the forward slot count
+        return _search(lambda s: block_mask(H, 0.15, seed + s), run_is(0, nsf))
+    if kind == "slots_bwd":     # BPTT run == the BPTT slot count
+        return _search(lambda s: block_mask(H, 0.15, seed + s), run_is(1, nsb))
+    if kind == "cuts":          # nwaves - 1 cut tiles in both plans
+        def ok(m):
+            p = _plans(m)
+            return p is not None and all(plan_stats(x, nw)[2] == nw - 1 for x in p)
+        return _search(lambda s: block_mask(H, 0.5, seed + s), ok)
+    if kind == "longest":       # one full unit band and one full column band over a thin diagonal
+        m = torch.zeros(1, H, H, dtype=torch.bool)
+        m[0, :16, :] = True
+        m[0, :, :16] = True
+        for i in range(0, H, 16):
+            m[0, i:i + 16, i:i + 16] = True
+        return m & block_mask(H, 1.0, seed)
+    if kind == "empty_tile":    # unit tile 1 and column tile 2 without a block
+        m = block_mask(H, 0.7, seed)
+        m[0, 16:32, :] = False
+        m[0, :, 32:48] = False
+        return m
+    raise ValueError(kind)
+
+
+def persist_mask(kind, H, seed=0):
+    """A fresh copy of the mask _persist_mask finds (cached per (kind, H, seed): the searches are
+    deterministic, and both the CPU reach test and the GPU cases ask for the same masks)."""
+    return _persist_mask(kind, H, seed).clone()
+
+
+SCase = collections.namedtuple("SCase", "cell T B bidir H act nslab seed slots kind bf16 form mask")
+SCase.B2 = property(lambda c: 2 * c.B if c.bidir else c.B)
+SCase.id = property(lambda c: "%s-%s%s-T%d-H%d-B2_%d-%s%s%s%s" % (
+    c.cell, c.kind, "-S%d" % c.slots if c.slots else "", c.T, c.H, c.B2, c.act,
+    "-slabs%d" % c.nslab if c.nslab > 1 else "", "-bf16" if c.bf16 else "",
+    "-gen" if c.mask == "gen" else ""))
+
+SPARSE_H = {16: (40, 22, 25), 32: (320, 322, 321), 64: (560, 562, 561)}      # vw 4, 2, 1 each
+SPARSE_KEEP = {16: 0.6, 32: 0.85, 64: 0.92}     # block keep rate: the fullest row needs S slots
+_SB2_ROT = ((6, 17, 34), (34, 6, 17), (17, 34, 6))
+
+
+def make_scase(cell, T, H, B2, act, slots=0, kind="blocks", nslab=1, seed=0, bf16=False,
+               form=(0, 0), mask="inject", bidir=None):
+    B, bd = ROWS_OF[B2] if bidir is None else ((B2 // 2, True) if bidir else (B2, False))
+    return SCase(cell, T, B, bd, H, "tanh" if cell == "lstm" else act, nslab, seed, slots, kind,
+                 bf16, form, mask)
+
+
+def sparse_fp32_cases():
+    """fp32 block-sparse steps: per cell 9 (H, B2) pairs at T = 3 — slots 16 / 32 / 64 x the three
+    load widths, the row classes rotating — then a table with an all -1 forward row and an all -1
+    BPTT row, T = 1, and dy in 3 slabs."""
+    out = []
+    for ci, cell in enumerate(CELLS):
+        for si, (S, Hs) in enumerate(SPARSE_H.items()):
+            for hi, H in enumerate(Hs):
+                act = ("relu", "tanh")[(ci + si + hi) % 2]
+                out.append(make_scase(cell, 3, H, _SB2_ROT[(si + ci) % 3][hi], act, S,
+                                      seed=70000 + 1000 * ci + 10 * si + hi))
+        out.append(make_scase(cell, 3, 40, 17, "relu", 16, "emptyrow", seed=70000 + 1000 * ci + 900))
+        out.append(make_scase(cell, 1, 25, 17, "tanh", 16, seed=70000 + 1000 * ci + 901))
+        out.append(make_scase(cell, 3, 322, 34, "relu", 32, nslab=3, seed=70000 + 1000 * ci + 902))
+    return out
+
+
+def sparse_bf16_cases():
+    """bf16 step products over a kmap (BF && SP): liGRU and LSTM, one case per slot count, each at
+    another row class; H a multiple of 8, even, odd (load_strip_h's three forms)."""
+    out = []
+    for ci, cell in enumerate(("ligru", "lstm")):
+        for i, (S, H, B2) in enumerate(((16, 40, 6), (32, 322, 17), (64, 561, 34))):
+            out.append(make_scase(cell, 3, H, B2, ("relu", "tanh")[(ci + i) % 2], S,
+                                  seed=76000 + 100 * ci + i, bf16=True))
+    return out
+
+
+def sparse_grid_cases():
+    """Sparse liGRU in the grid-synchronised loops (default environment, fp32, B2 <= 16)."""
+    return [make_scase("ligru", 3, 48, 6, "relu", 16, seed=77000, form=(2, 2)),
+            make_scase("ligru", 3, 550, 16, "tanh", 64, seed=77001, form=(2, 2))]
+
+
+def persist_cases():
+    """The persistent liGRU loops (bf16 steps, form 1), relu and tanh in turn: a C3-like HCGS plan,
+    H = 576 at either slot limit, register-only and tiny plans, ragged H with 34 workgroups, 7 cut
+    tiles, a run fixed by the longest tile, a tile without a block, T = 1 and 2, dy in 2 slabs, the
+    mixed forms (1, 0) and the generated dropout mask (tests/test_gpu_rnn_sparse_kernels.py, d)."""
+    P = dict(cell="ligru", bf16=True, form=(1, 1))
+    rows = [  # (kind, T, H, B2, bidir, extra)
+        ("c3", 4, 550, 16, True, {}),
+        ("slots_fwd", 3, 576, 3, False, {}),
+        ("slots_bwd", 3, 576, 3, False, {}),
+        ("dense", 3, 96, 17, False, {}),
+        ("dense", 3, 32, 6, True, {}),
+        ("dense", 3, 2, 1, False, {}),
+        ("blocks", 3, 18, 34, True, {}),
+        ("blocks", 3, 34, 34, True, {}),
+        ("blocks", 3, 46, 34, True, {}),
+        ("cuts", 3, 160, 6, True, {}),
+        ("longest", 3, 256, 3, False, {}),
+        ("empty_tile", 3, 96, 6, True, {}),
+        ("dense", 1, 96, 6, True, {}),
+        ("dense", 2, 96, 6, True, {}),
+        ("dense", 3, 96, 6, True, dict(nslab=2)),
+        ("c3", 3, 550, 6, True, dict(nslab=2)),
+        ("dense", 3, 96, 12, True, dict(nslab=3, slots=16, form=(1, 0))),
+        ("blocks", 3, 96, 6, True, dict(mask="gen")),
+    ]
+    out = []
+    for i, (kind, T, H, B2, bidir, extra) in enumerate(rows):
+        kw = dict(P, kind=kind, seed=78000 + i, bidir=bidir)
+        kw.update(extra)
+        cell = kw.pop("cell")
+        out.append(make_scase(cell, T, H, B2, ("relu", "tanh")[i % 2], **kw))
+    return out
+
+
+def case_mask(c):
+    """The case's U masks (G, H, H) bool: per-gate masks for the step tables, one shared mask for
+    the persistent loops."""
+    G = CELLS[c.cell][1]
+    if c.form[0] == 1:
+        return persist_mask(c.kind, c.H, c.seed).expand(G, c.H, c.H).clone()
+    m = block_mask(c.H, SPARSE_KEEP[c.slots], c.seed + 3, G)
+    if c.kind == "emptyrow":
+        m[:, 16:32, :] = False      # forward tiles of units 16..31: no block (all gates)
+        m[:, :, :16] = False        # BPTT tiles of columns 0..15: no block
+    return m
+
+
+def case_tables(c, umask):
+    """(kmaps, plans) of a case: the step tables of pkc.engine.rnn_kmaps ("force": a table whenever
+    it fits) when the case has a slot count, the persistent plans when it expects form 1."""
+    from pkc import engine as E
+    kmaps = E.rnn_kmaps(list(umask), CAND.get(c.cell), "force") if c.slots else None
+    plans = E.persist_plans(umask.any(0).numpy()) if 1 in c.form else None
+    return kmaps, plans
+
+
+def sparse_inputs(c):
+    """make_inputs with the masked U (the kernels' contract: unlisted entries are zero) and the mask."""
+    inp = make_inputs(c)
+    inp["umask"] = case_mask(c)
+    inp["U"] = inp["U"] * inp["umask"]
+    return inp
 
 
 def make_inputs(c, ln=False):
@@ -183,10 +415,15 @@ def _dev(t, dtype=None):
 class Layer:
     """One layer's buffers and the argument struct of both entry points.
     mask: "inject" (inp["mask"] through drop_mask_in), "gen" (the library's generator) or None
-    (drop_p = 0); ln: LayerNorm of h with inp["gamma"] / inp["beta"]; bf16: bf16 step products."""
+    (drop_p = 0); ln: LayerNorm of h with inp["gamma"] / inp["beta"]; bf16: bf16 step products.
+    umask: (G, H, H) U mask — U and U_h are multiplied by it (the block-sparse kernels' contract:
+    unlisted entries are zero); kmaps: (kmap_fwd, s_fwd, kmap_bwd, s_bwd) of pkc.engine.rnn_kmaps;
+    plans: (persist_fwd, persist_bwd) of pkc.engine.persist_plans (persist_kb from the geometry).
+    The tables live in ordinary device tensors."""
 
     def __init__(self, cell, T, B, H, bidir, act, inp, ln=False, bf16=False, mask="inject",
-                 train=True, drop_p=0.2, nslab=1, slab_seed=0, step=0, seed=1234, stream_id=77):
+                 train=True, drop_p=0.2, nslab=1, slab_seed=0, step=0, seed=1234, stream_id=77,
+                 umask=None, kmaps=None, plans=None):
         self.cell, self.T, self.B, self.H, self.bidir = cell, T, B, H, bool(bidir)
         cid, G = CELLS[cell]
         self.G, self.B2 = G, 2 * B if bidir else B
@@ -194,7 +431,8 @@ class Layer:
         self.D = D
         n = B2 * H
         self.wpre = _dev(inp["wpre"])
-        self.U = _dev(inp["U"])
+        self.U_cpu = inp["U"] if umask is None else inp["U"] * umask
+        self.U = _dev(self.U_cpu)
         self.bufs = {}
         mk = self._mk
         mk("drop_mask", n)
@@ -233,7 +471,7 @@ class Layer:
                 setattr(a, k, self.bufs[k].p)
         if bf16:
             # U_h = RNE(U), made with torch (the caller keeps these copies current)
-            self.U_h = _dev(inp["U"], torch.bfloat16)
+            self.U_h = _dev(self.U_cpu, torch.bfloat16)
             a.step_bf16 = 1
             for k, sz in (("hs_h", (T + 1) * n), ("ut_h", G * H * H), ("dgates_h", G * T * n)):
                 mk(k, sz, torch.bfloat16)
@@ -249,6 +487,19 @@ class Layer:
             flat[s * stride:s * stride + cnt] = self.dy_parts[s].reshape(-1)
         self.dy = _dev(flat)
         a.dy, a.dy_nslab, a.dy_slab_stride = self.dy.data_ptr(), nslab, stride if nslab > 1 else 0
+        self.tables = {}
+        if kmaps is not None:
+            for name, tab, S in (("kmap_fwd", kmaps[0], kmaps[1]), ("kmap_bwd", kmaps[2], kmaps[3])):
+                if tab is not None:
+                    self.tables[name] = _dev(tab.to(torch.int32))
+                    setattr(a, name, self.tables[name].data_ptr())
+                    setattr(a, name.replace("kmap_", "kmap_s_"), S)
+        if plans is not None:
+            from pkc import engine as E
+            for name, tab in zip(("persist_fwd", "persist_bwd"), plans):
+                self.tables[name] = _dev(torch.as_tensor(tab, dtype=torch.int32))
+                setattr(a, name, self.tables[name].data_ptr())
+            a.persist_kb = E.persist_geometry()[1]
         self.a = a
 
     def _mk(self, name, n, dtype=torch.float32):

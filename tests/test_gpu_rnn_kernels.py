@@ -87,23 +87,27 @@ def _exact_checks(lay, c, inp, bf16, injected=True):
         assert torch.equal(lay.get("ut_h", True), inp["U"].transpose(1, 2).to(bf)), "ut_h != RNE(U^T)"
 
 
-def _run(c, ln=False, bf16=False, form=0, inp=None):
-    """Forward + backward of one case, every check of the module docstring; returns the layer."""
+def _run(c, ln=False, bf16=False, form=0, inp=None, mask="inject", **tables):
+    """Forward + backward of one case, every check of the module docstring; returns the layer.
+    form: the expected pkc_rnn_persist_form, one number or a (forward, BPTT) pair; tables: the
+    Layer's umask / kmaps / plans; mask "gen": the library's own dropout mask."""
     inp = RK.make_inputs(c, ln) if inp is None else inp
     lay = RK.Layer(c.cell, c.T, c.B, c.H, c.bidir, c.act, inp, ln=ln, bf16=bf16, nslab=c.nslab,
-                   slab_seed=c.seed)
-    assert lay.form(0) == form and lay.form(1) == form, \
-        "pkc_rnn_persist_form %d / %d, expected %d" % (lay.form(0), lay.form(1), form)
+                   slab_seed=c.seed, mask=mask, **tables)
+    forms = (form, form) if isinstance(form, int) else tuple(form)
+    assert (lay.form(0), lay.form(1)) == forms, \
+        "pkc_rnn_persist_form %d / %d, expected %d / %d" % ((lay.form(0), lay.form(1)) + forms)
     lay.forward()
     lay.backward()
     n4 = 4 * c.B2 * c.H
-    if form == 2:
+    if 2 in forms:
         word = lay.get("work").reshape(-1)[n4 + 1:n4 + 2].view(torch.int32)
         assert int(word[0]) == 0, "a grid-synchronised loop timed out"
-    _exact_checks(lay, c, inp, bf16)
-    s = _state(lay, c, inp, bf16, ln, inp["mask"])
+    _exact_checks(lay, c, inp, bf16, injected=mask == "inject")
+    drop = inp["mask"] if mask == "inject" else lay.get("drop_mask", True)
+    s = _state(lay, c, inp, bf16, ln, drop)
     lnp = dict(gamma=inp["gamma"].double(), beta=inp["beta"].double(), eps=1e-6) if ln else None
-    tag = c.id + (" LN" if ln else "") + (" bf16" if bf16 else "") + (" grid" if form == 2 else "")
+    tag = c.id + (" LN" if ln else "") + (" bf16" if bf16 else "") + (" grid" if 2 in forms else "")
     _compare(tag, RK.restate(c.cell, c.act, s, lnp), [])
     lay.check_guards()
     first = lay.snapshot()

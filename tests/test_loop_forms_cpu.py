@@ -102,3 +102,58 @@ def test_environment_switches(monkeypatch):
                        ut_h=True, dgates_h=True)) == (0, 0)
     monkeypatch.setenv("PKC_RNN_LIGRU_GRID", "0")
     assert _form(_args(L.CELL_LIGRU, 550, 8, True)) == (0, 0)
+
+
+# ------------------------------------------------------------------ form 1: the persistent liGRU loops
+def _persist_args(H=550, B=8, bidir=True, **kw):
+    """liGRU with bf16 step products, both plans and persist_kb = the forward slot count
+    (pkc_rnn_persist_geometry): everything rnn_persist_ok asks for."""
+    from pkc import _lib as L
+    from pkc.engine import persist_geometry
+    base = dict(step_bf16=1, hs_h=True, U_h=True, ut_h=True, dgates_h=True, persist_fwd=True,
+                persist_bwd=True, persist_kb=persist_geometry()[1])
+    base.update(kw)
+    return _args(L.CELL_LIGRU, H, B, bidir, **base)
+
+
+def test_form1_accepts_the_persistent_ligru_layers():
+    from pkc.engine import persist_geometry
+    hmax = persist_geometry()[4]
+    assert _form(_persist_args()) == (1, 1)                          # C3
+    assert _form(_persist_args(hmax, 3, False)) == (1, 1)            # the largest H, one direction
+    assert _form(_persist_args(2, 1, False)) == (1, 1)
+    assert _form(_persist_args(96, 17, True)) == (1, 1)              # 34 rows: no row limit
+    assert _form(_persist_args(kmap_fwd=True, kmap_bwd=True)) == (1, 1)      # (tables beside plans)
+    assert _form(_persist_args(dy_nslab=2, dy_slab_stride=1 << 20)) == (1, 1)
+
+
+@pytest.mark.parametrize("case", ["H578", "odd_H", "persist_kb", "layernorm", "no_hs_h", "no_ut_h",
+                                  "no_dgates_h", "no_plan_bwd", "fp32_steps", "lstm"])
+def test_form1_refusals(case, monkeypatch):
+    from pkc import _lib as L
+    from pkc.engine import persist_geometry
+    monkeypatch.setenv("PKC_RNN_LIGRU_GRID", "0")       # (what form 1 falls back to: per step)
+    nsf = persist_geometry()[1]
+    a, want = {
+        "H578": lambda: (_persist_args(578), (0, 0)),
+        "odd_H": lambda: (_persist_args(549), (0, 0)),
+        "persist_kb": lambda: (_persist_args(persist_kb=nsf - 1), (0, 0)),
+        "layernorm": lambda: (_persist_args(ln_gamma=True), (0, 0)),
+        "no_hs_h": lambda: (_persist_args(hs_h=False), (0, 0)),
+        # the BPTT's own operands: the forward loop does not need them
+        "no_ut_h": lambda: (_persist_args(ut_h=False), (1, 0)),
+        "no_dgates_h": lambda: (_persist_args(dgates_h=False), (1, 0)),
+        "no_plan_bwd": lambda: (_persist_args(persist_bwd=False), (1, 0)),
+        "fp32_steps": lambda: (_persist_args(step_bf16=0), (0, 0)),
+        "lstm": lambda: (_args(L.CELL_LSTM, 550, 8, True, step_bf16=1, hs_h=True, U_h=True,
+                               ut_h=True, dgates_h=True, persist_fwd=True, persist_bwd=True,
+                               persist_kb=nsf), (0, 0)),
+    }[case]()
+    assert _form(a) == want
+
+
+def test_form1_with_three_dy_slabs_keeps_the_forward_loop():
+    """dy_nslab = 3: the BPTT loop sums two slabs at the most, so the forward stays form 1 and the
+    BPTT takes the per-step launches (bf16 steps: no grid-synchronised liGRU form either)."""
+    assert _form(_persist_args(dy_nslab=3, dy_slab_stride=1 << 20)) == (1, 0)
+    assert _form(_persist_args(dy_nslab=2, dy_slab_stride=1 << 30)) == (1, 0)    # 32-bit offsets
